@@ -10,6 +10,13 @@ of the stream (weak scaling, tables replicated) and the counters are
 all-reduced over RCCL once at the end of the timed region.
 
 Prints ONE JSON line on rank 0 (contract in the task statement).
+
+A plain run sets up, warms up, times the steps and prints the line (the
+roofline section prices the timed steps' own HIP-event durations with the
+committed PMC records: no run of its own).  --full adds what takes runs of
+its own on the host-core oracle: the CPU baseline, the parity sample and the
+§8d algorithmic bytes.  --dump-outputs DIR writes what the last timed step
+computed (a fixed, seeded sample of each output array) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -208,6 +215,147 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
+DUMP_SAMPLE = 1 << 20     # headers per dumped array (8 MiB as float64)
+DUMP_RECORDS = 1 << 16    # monitor records dumped (--notify)
+
+
+def dump_outputs(path, dp, out, out6, monitor, counters):
+    """--dump-outputs: what the last timed step left in the arrays a caller of
+    the step receives, as float64 path/<name>.npy (every int32 / u32 value
+    exact): verdict and identity (u32), with them the CT byte and the notify
+    word where the run produces them, at the same DUMP_SAMPLE seeded indices
+    of the batch (the whole array when shorter); `_v6` for the IPv6 batch;
+    the first DUMP_RECORDS monitor records with their header indices and the
+    step's record count (--notify); and the metrics rows (reason, dir, count,
+    bytes) the timed steps counted.  At most 4 sampled arrays of 8 MiB (c5
+    with --ct-apply --notify) and 4.5 MiB of records: under 64 MB in all."""
+    import torch
+    from cilium_amd import metricsmap
+    os.makedirs(path, exist_ok=True)
+
+    def save(name, a):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, np.float64))
+
+    for sfx, o in (("", out), ("_v6", out6)):
+        if o is None:
+            continue
+        nn = o.verdict.numel()
+        idx = None
+        if nn > DUMP_SAMPLE:
+            idx = torch.from_numpy(np.sort(np.random.default_rng(0xD0).integers(
+                0, nn, DUMP_SAMPLE))).to(o.verdict.device)
+        for name, t in (("verdict", o.verdict), ("identity", o.identity),
+                        ("ct", o.ct), ("notify", o.notify)):
+            if t is None:
+                continue
+            a = (t if idx is None else t[idx]).cpu().numpy()
+            save(name + sfx, a.view(np.uint32) if name == "identity" else a)
+    if monitor is not None:
+        rec, ridx, cnt = monitor
+        k = min(int(cnt.item()), DUMP_RECORDS)
+        save("monitor_count", cnt.cpu().numpy())
+        save("monitor_records", rec[:k].cpu().numpy())
+        save("monitor_index", ridx[:k].cpu().numpy())
+    if counters:   # (folded by cfc_counters_sync after the timed steps)
+        save("metrics", np.array(metricsmap.dump_rows(dp), np.uint64).reshape(-1, 4))
+
+
+def oracle_leg(args, tables, mode, ep_lxc, world, n, n6, v6c5, hdr, out, h6, batch6, out6,
+               monitor, kern_ms):
+    """--full: the host-core oracle on the first headers of the batch — the
+    CPU baseline, the parity of the last timed launch's verdicts and
+    identities (and monitor records) with it, and the §8d algorithmic bytes
+    from its lookup counts.  Returns the three as a dict."""
+    # ---- algorithmic bytes per header from the oracle's lookup counts (L),
+    #      and the host-core baseline + a parity check on the same sample
+    from cilium_amd import synth as S
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    import oracle as O
+    s, d, p, m, tf = hdr
+    nt_rec, nt_idx = monitor
+    samp = args.cpu_sample if (world == 1 and not args.no_cpu) else 200_000
+    samp6 = samp
+    samp = min(samp, n)
+    hs = S.unpack_v4(s[:samp].cpu().numpy(), d[:samp].cpu().numpy(),
+                     p[:samp].cpu().numpy(), m[:samp].cpu().numpy())
+    hs.tcpflags = (tf[:samp].cpu().numpy() if tf is not None
+                   else np.zeros(samp, np.uint8))
+    orc = O.Oracle(tables)
+    # every core this process may use: OMP_NUM_THREADS where the host gives
+    # the process a share of a larger machine, else the affinity mask
+    cores = int(os.environ.get("OMP_NUM_THREADS", 0)) or len(os.sched_getaffinity(0))
+    # the timed run computes what the engine computes (no lookup counting);
+    # the lookup counts for the §8d bytes come from a second, untimed run
+    c0 = time.perf_counter()
+    if n:
+        oa, ov, oi = orc.classify(hs, mode, ep_lxc, nthreads=cores)
+    cpu_s = time.perf_counter() - c0
+    lk = orc.classify(hs, mode, ep_lxc, nthreads=cores, want_lookups=True)[3] if n \
+        else np.zeros(1)
+    # the timed region's last launch wrote `out` for this same batch
+    # (with --ct-apply the tables moved on during the timed steps: the CT
+    # parity of classify + apply is tests/test_gpu_fullsize.py's)
+    parity = None if (args.ct_apply or not n) else bool(np.array_equal(out.verdict[:samp].cpu().numpy(), ov) and
+                  np.array_equal(out.identity[:samp].cpu().numpy().view(np.uint32), oi))
+    if v6c5:
+        # the IPv6 sample's tuples as the last step classified them (its new
+        # flows' ports re-drawn per step)
+        pp = batch6.ports[:len(h6)].cpu().numpy().view(np.uint32)
+        h6.sport, h6.dport = (pp & 0xFFFF).astype(np.uint16), (pp >> 16).astype(np.uint16)
+    if args.notify:   # the sample's monitor records, every field
+        _, ov2, oi2, ow = orc.classify(hs, mode, ep_lxc, nthreads=cores,
+                                       want_notify=True)
+        orec, oidx = orc.events(hs, mode, ep_lxc, ov2, oi2, ow)
+        k = len(oidx)
+        grec = nt_rec[:k].cpu().numpy()
+        gidx = nt_idx[:k].cpu().numpy().astype(np.uint64)
+        parity = parity and bool(np.array_equal(gidx, oidx) and np.array_equal(
+            np.ascontiguousarray(grec).view(np.uint8).reshape(-1),
+            np.ascontiguousarray(orec).view(np.uint8).reshape(-1)))
+    mean_l = float(lk.mean())
+    b_hdr = S_IN + S_OUT + 64.0 * mean_l
+    algo_bytes = n * b_hdr
+    if n6:   # the IPv6 half: 40 B in per header, its own lookup counts
+        s6 = min(samp6, n6, len(h6))
+        hs6 = S.take(h6, slice(0, s6))
+        c1 = time.perf_counter()
+        o6a, o6v, o6i = orc.classify(hs6, mode, ep_lxc, nthreads=cores)
+        cpu_s += time.perf_counter() - c1
+        lk6 = orc.classify(hs6, mode, ep_lxc, nthreads=cores, want_lookups=True)[3]
+        parity = parity and bool(
+            np.array_equal(out6.verdict[:s6].cpu().numpy(), o6v) and
+            np.array_equal(out6.identity[:s6].cpu().numpy().view(np.uint32), o6i))
+        b6 = 40 + S_OUT + 64.0 * float(lk6.mean())
+        algo_bytes += n6 * b6
+        mean_l = (n * mean_l + n6 * float(lk6.mean())) / (n + n6)
+        b_hdr = algo_bytes / (n + n6)
+        samp += s6
+    algo_gbs = algo_bytes / (kern_ms * 1e-3) / 1e9
+    return {
+        # SURVEY.md §8d's accounting — 24 B of header I/O + a 64 B line per
+        # map lookup — is not a bound here: the tables are cache-resident,
+        # so most lookups never reach HBM (the roofline's "frac" prices them
+        # at the cache that serves them).  Kept as the §8d bytes per header
+        # only; its rate is labelled as what it is
+        "algorithmic": {
+            "bytes_per_header": round(b_hdr, 2),
+            "mean_lookups_per_header": round(mean_l, 4),
+            "sec8d_equivalent_gbs_not_a_bound": round(algo_gbs, 1),
+        },
+        "cpu_baseline": None if (world > 1 or args.no_cpu) else {
+            "value": round(samp / cpu_s / 1e6, 3),
+            "unit": "Mpps",
+            "cores": cores,
+            "kind": "port",
+            "sample": f"first {samp} headers of the same stream through the C "
+                      f"restatement (oracle/cfc_oracle.c), {cores} OpenMP threads",
+            # the reference itself, measured where it can run (SURVEY.md §8d (1))
+            "reference_bpf": reference_bpf_baseline(),
+        },
+        "parity_sample_ok": parity,
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -216,9 +364,19 @@ def main():
     ap.add_argument("--headers", type=int, default=64 << 20)
     ap.add_argument("--mode", default="full",
                     choices=["ingress", "egress", "xdp", "full"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run the host-core oracle on a sample of the stream: "
+                         "cpu_baseline, parity_sample_ok and roofline.algorithmic "
+                         "(a plain run leaves these keys out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed, as "
+                         "float64 DIR/<name>.npy: verdicts, identities (and CT bytes, "
+                         "notify words, monitor records) at DUMP_SAMPLE seeded indices "
+                         "of the batch, the metrics counters of the timed steps")
     ap.add_argument("--cpu-sample", type=int, default=2_000_000,
-                    help="headers timed on the host-core oracle (rank 0, N=1)")
-    ap.add_argument("--no-cpu", action="store_true")
+                    help="--full: headers timed on the host-core oracle (rank 0, N=1)")
+    ap.add_argument("--no-cpu", action="store_true",
+                    help="--full: no cpu_baseline (parity on a 200k sample)")
     ap.add_argument("--seed", type=int, default=2)
     ap.add_argument("--notify", action="store_true",
                     help="also produce every monitor record — drop_notify and "
@@ -488,74 +646,22 @@ def main():
         f"{call_ms:.3f} ms = classify {kern_ms:.3f} + counters {count_ms:.3f}; "
         f"{mpps:.0f} Mpps")
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs if rank == 0 else
+                     os.path.join(args.dump_outputs, f"rank{rank}"),
+                     dp, out if n else None, out6 if n6 else None,
+                     (nt_rec, nt_idx, nt_cnt) if args.notify else None,
+                     counters=world == 1 and not args.ct_apply)
+
     if rank != 0:
         dist.destroy_process_group()
         return
 
-    # ---- algorithmic bytes per header from the oracle's lookup counts (L),
-    #      and the host-core baseline + a parity check on the same sample
-    sys.path.insert(0, os.path.join(ROOT, "oracle"))
-    import oracle as O
-    samp = args.cpu_sample if (world == 1 and not args.no_cpu) else 200_000
-    samp6 = samp
-    samp = min(samp, n)
-    hs = S.unpack_v4(s[:samp].cpu().numpy(), d[:samp].cpu().numpy(),
-                     p[:samp].cpu().numpy(), m[:samp].cpu().numpy())
-    hs.tcpflags = (tf[:samp].cpu().numpy() if tf is not None
-                   else np.zeros(samp, np.uint8))
-    orc = O.Oracle(tables)
-    # every core this process may use: the GPU pool gives a one-GPU box a
-    # 16-core share and says so in OMP_NUM_THREADS (nproc shows the whole
-    # machine there); elsewhere the affinity mask
-    cores = int(os.environ.get("OMP_NUM_THREADS", 0)) or len(os.sched_getaffinity(0))
-    # the timed run computes what the engine computes (no lookup counting);
-    # the lookup counts for the §8d bytes come from a second, untimed run
-    c0 = time.perf_counter()
-    if n:
-        oa, ov, oi = orc.classify(hs, mode, ep_lxc, nthreads=cores)
-    cpu_s = time.perf_counter() - c0
-    lk = orc.classify(hs, mode, ep_lxc, nthreads=cores, want_lookups=True)[3] if n \
-        else np.zeros(1)
-    # the timed region's last launch wrote `out` for this same batch
-    # (with --ct-apply the tables moved on during the timed steps: the CT
-    # parity of classify + apply is tests/test_gpu_fullsize.py's)
-    parity = None if (args.ct_apply or not n) else bool(np.array_equal(out.verdict[:samp].cpu().numpy(), ov) and
-                  np.array_equal(out.identity[:samp].cpu().numpy().view(np.uint32), oi))
-    if v6c5:
-        # the IPv6 sample's tuples as the last step classified them (its new
-        # flows' ports re-drawn per step)
-        pp = batch6.ports[:len(h6)].cpu().numpy().view(np.uint32)
-        h6.sport, h6.dport = (pp & 0xFFFF).astype(np.uint16), (pp >> 16).astype(np.uint16)
-    if args.notify:   # the sample's monitor records, every field
-        _, ov2, oi2, ow = orc.classify(hs, mode, ep_lxc, nthreads=cores,
-                                       want_notify=True)
-        orec, oidx = orc.events(hs, mode, ep_lxc, ov2, oi2, ow)
-        k = len(oidx)
-        grec = nt_rec[:k].cpu().numpy()
-        gidx = nt_idx[:k].cpu().numpy().astype(np.uint64)
-        parity = parity and bool(np.array_equal(gidx, oidx) and np.array_equal(
-            np.ascontiguousarray(grec).view(np.uint8).reshape(-1),
-            np.ascontiguousarray(orec).view(np.uint8).reshape(-1)))
-    mean_l = float(lk.mean())
-    b_hdr = S_IN + S_OUT + 64.0 * mean_l
-    algo_bytes = n * b_hdr
-    if n6:   # the IPv6 half: 40 B in per header, its own lookup counts
-        s6 = min(samp6, n6, len(h6))
-        hs6 = S.take(h6, slice(0, s6))
-        c1 = time.perf_counter()
-        o6a, o6v, o6i = orc.classify(hs6, mode, ep_lxc, nthreads=cores)
-        cpu_s += time.perf_counter() - c1
-        lk6 = orc.classify(hs6, mode, ep_lxc, nthreads=cores, want_lookups=True)[3]
-        parity = parity and bool(
-            np.array_equal(out6.verdict[:s6].cpu().numpy(), o6v) and
-            np.array_equal(out6.identity[:s6].cpu().numpy().view(np.uint32), o6i))
-        b6 = 40 + S_OUT + 64.0 * float(lk6.mean())
-        algo_bytes += n6 * b6
-        mean_l = (n * mean_l + n6 * float(lk6.mean())) / (n + n6)
-        b_hdr = algo_bytes / (n + n6)
-        samp += s6
-    algo_gbs = algo_bytes / (kern_ms * 1e-3) / 1e9
-    layout = {1: "dir24_8", 2: "trie"}.get(st["lpm4_layout"], "none")
+    full = None
+    if args.full:
+        full = oracle_leg(args, tables, mode, ep_lxc, world, n, n6, v6c5, (s, d, p, m, tf),
+                          out, h6, batch6, out6, (nt_rec, nt_idx), kern_ms)
+    layout ={1: "dir24_8", 2: "trie"}.get(st["lpm4_layout"], "none")
     # ---- the bound: the chip's random-request rate for the tables' size.
     # Per kernel: its working set (device tables; CT slots with their timer
     # and accounting words), the measured random-load ceiling for that size,
@@ -662,31 +768,14 @@ def main():
                 "peak_gbs": HBM_PEAK_GBS,
                 "frac": round(stream_b / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
             },
-            # SURVEY.md §8d's accounting — 24 B of header I/O + a 64 B line per
-            # map lookup — is not a bound here: the tables are cache-resident,
-            # so most lookups never reach HBM ("frac" above prices them at
-            # the cache that serves them).  Kept as the §8d bytes per header
-            # only; its rate is labelled as what it is
-            "algorithmic": {
-                "bytes_per_header": round(b_hdr, 2),
-                "mean_lookups_per_header": round(mean_l, 4),
-                "sec8d_equivalent_gbs_not_a_bound": round(algo_gbs, 1),
-            },
+            # (--full: the §8d bytes per header from the oracle's lookup counts)
+            **({"algorithmic": full["algorithmic"]} if full else {}),
             "kernel_ms_per_launch": round(kern_ms, 4),
             "count_kernels_ms_per_launch": round(count_ms, 4),
             "call_ms_per_launch": round(call_ms, 4),
         },
-        "cpu_baseline": None if (world > 1 or args.no_cpu) else {
-            "value": round(samp / cpu_s / 1e6, 3),
-            "unit": "Mpps",
-            "cores": cores,
-            "kind": "port",
-            "sample": f"first {samp} headers of the same stream through the C "
-                      f"restatement (oracle/cfc_oracle.c), {cores} OpenMP threads",
-            # the reference itself, measured where it can run
-            "reference_bpf": reference_bpf_baseline(),
-        },
-        "parity_sample_ok": parity,
+        # (--full: the host-core oracle's rate and the parity sample)
+        **({k: full[k] for k in ("cpu_baseline", "parity_sample_ok")} if full else {}),
         "monitor_records_per_step_per_gpu": int(nt_cnt.item()) if args.notify else None,
     }
     if args.ct_apply:   # the step is classify + cfc_ct_apply_v4 (+ cfc_ct_gc)

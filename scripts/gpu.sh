@@ -9,7 +9,8 @@
 #   tests                     the whole -m gpu suite
 #   tests:ARGS                pytest -m gpu with ARGS (e.g. "tests:tests/test_gpu_lb.py -k v6")
 #   smoke                     __graft_entry__.smoke()
-#   bench:NAME:ARGS           python bench.py ARGS > OUTDIR/NAME.json
+#   bench:NAME:ARGS           python bench.py ARGS > OUTDIR/NAME.json (--full in ARGS for the
+#                             CPU baseline, the parity sample and the §8d bytes)
 #   kt:NAME:ARGS              rocprofv3 --kernel-trace --stats of bench.py ARGS -> OUTDIR/NAME/kt
 #   pmc:NAME:ARGS             the PMC passes (scripts/pmc_groups) of bench.py ARGS -> OUTDIR/NAME/pmcN
 #   py:NAME:SCRIPT ARGS       python -u SCRIPT ARGS > OUTDIR/NAME.log (ubench drivers, debug scripts)
