@@ -866,17 +866,26 @@ __global__ __launch_bounds__(BLOCK, WAVES_PER_SIMD) void k_classify_v4(
 
 // ---- counters ---------------------------------------------------------------
 // k_hist: the exact sums behind one key range of one key array, per slice of
-// the batch: an LDS histogram of up to HIST_RANGE u64 slots, one packed
-// {packets << 40 | bytes} atomic per header (a slice is at most 2^24
-// headers of <= 65535 bytes, so neither half carries), written as a partial
-// slab; k_hist_reduce sums the slabs per key and adds them into the counter
-// block.  One launch runs every job (policy ranges of each stage, identity
-// ranges) side by side: blockIdx.y is the job, blockIdx.x the slice.
+// the batch: an LDS histogram of up to HIST_RANGE u32 slots, one returning
+// {1 << 21 | len} atomic per header (classify.hpp HistSlot), written as a
+// partial slab; k_hist_reduce unpacks the slabs' fields, sums them per key
+// in u64 and adds them into the counter block.  A hot key overflows its
+// slot's fields (the byte field after 2 MiB, the packet field after 2047
+// packets): the thread whose add did it sees it in the returned value and
+// counts the carry / wrap in the workgroup's escape table (LDS, open
+// addressing, HIST_ESC_SLOTS entries {key, carries, wraps}), which the
+// workgroup flushes at its end with one global atomic pair per entry
+// straight into the counters (the packet delta 2^11 * wraps - carries may
+// be negative: added as a two's complement u64; nothing reads the counters
+// before k_hist_reduce has added the rest).  An escape that finds no entry
+// within 8 probes adds its delta to the counters itself.  One launch runs
+// every job (policy ranges of each stage, identity ranges) side by side:
+// blockIdx.y is the job, blockIdx.x the slice.
 namespace {
 
 struct HistJob {
     const uint32_t *keys;
-    uint64_t poff;        // first u64 of the job's partial slabs
+    uint64_t poff;        // first u32 of the job's partial slabs
     uint32_t lo, cnt;     // key range [lo, lo + cnt)
     uint32_t kind;        // 0 policy entry, 1 identity (dense << 1 | drop)
     uint32_t packed;      // keys carry len in bits 16-31 (else meta does)
@@ -885,31 +894,106 @@ constexpr int HIST_JOBS_MAX = 12;
 struct HistJobs {
     HistJob j[HIST_JOBS_MAX];
 };
-constexpr uint64_t BYTES_MASK = (1ull << 40) - 1;
-constexpr uint64_t SLICE_MAX = 1ull << 24;
+// A slot's fields hold any count modulo their width, so the slots bound a
+// slice no more; the escape table does: it counts a workgroup's carries and
+// wraps in u32, at most one of each per header of the slice.
+constexpr uint64_t SLICE_MAX = 1ull << 31;
 
-__device__ __forceinline__ void hist_add(unsigned long long *s, const HistJob &jb,
-                                         uint32_t w, uint32_t m)
+// the counter pair of a job's key
+__device__ __forceinline__ unsigned long long *hist_dst(const HistJob &jb, uint32_t key,
+                                                        uint64_t *g_ctr, uint64_t *g_id,
+                                                        uint32_t id_dir)
 {
-    uint32_t k, len;
+    return reinterpret_cast<unsigned long long *>(
+        jb.kind == 0 ? g_ctr + 2ull * key : g_id + id_index(id_dir, key >> 1, key & 1));
+}
+
+// the workgroup's LDS: the escape table, then the job's slots
+struct HistLds {
+    uint32_t *ek, *ec, *ew;   // escape entries: slot index (NONE free), carries, wraps
+    uint32_t *s;
+};
+__device__ __forceinline__ HistLds hist_lds()
+{
+    uint32_t *b = reinterpret_cast<uint32_t *>(cfc_smem);
+    return HistLds{b, b + HIST_ESC_SLOTS, b + 2 * HIST_ESC_SLOTS, b + 3 * HIST_ESC_SLOTS};
+}
+
+// one header's add: the slot index (r >= jb.cnt: not this job's), its len,
+// and what the slot held before (0 when nothing was added: spills nothing)
+struct HistAdd {
+    uint32_t r, len, old;
+};
+__device__ __forceinline__ HistAdd hist_add(uint32_t *s, const HistJob &jb, uint32_t w,
+                                            uint32_t m)
+{
+    HistAdd a;
+    uint32_t k;
     if (jb.packed) {
         k = w & 0xFFFF;
-        len = w >> 16;
+        a.len = w >> 16;
     } else {
         k = w;
-        len = m >> 16;
+        a.len = m >> 16;
     }
-    const uint32_t r = k - jb.lo;
-    if (r < jb.cnt)
-        atomicAdd(&s[r], (1ull << 40) | len);
+    a.r = k - jb.lo;
+    // (KEY_NONE's low half is the last identity key, a drop of identity
+    // ID_PACK_LIMIT - 1: that key with len 65535 is the one word id_key
+    // leaves to id_count)
+    a.old = a.r < jb.cnt && w != KEY_NONE ? atomicAdd(&s[a.r], HistSlot::inc(a.len)) : 0u;
+    return a;
+}
+__device__ __forceinline__ bool hist_spills(const HistAdd &a)
+{
+    uint32_t carry, wrap;
+    HistSlot::spill(a.old, a.len, carry, wrap);
+    return (carry | wrap) != 0;
+}
+// (rare) this add overflowed a field of its slot
+__device__ __forceinline__ void hist_escape(const HistLds &L, const HistJob &jb,
+                                            const HistAdd &a, uint64_t *g_ctr, uint64_t *g_id,
+                                            uint32_t id_dir)
+{
+    uint32_t carry, wrap;
+    HistSlot::spill(a.old, a.len, carry, wrap);
+    if (!(carry | wrap))
+        return;
+    uint32_t h = fmix32(a.r) & (HIST_ESC_SLOTS - 1);
+    for (int p = 0; p < 8; p++) {
+        uint32_t cur = L.ek[h];
+        if (cur == NONE) {
+            cur = atomicCAS(&L.ek[h], NONE, a.r);
+            if (cur == NONE)
+                cur = a.r;
+        }
+        if (cur == a.r) {
+            if (carry)
+                atomicAdd(&L.ec[h], carry);
+            if (wrap)
+                atomicAdd(&L.ew[h], wrap);
+            return;
+        }
+        h = (h + 1) & (HIST_ESC_SLOTS - 1);
+    }
+    unsigned long long *d = hist_dst(jb, jb.lo + a.r, g_ctr, g_id, id_dir);
+    atomicAdd(d, (unsigned long long)HistSlot::esc_packets(carry, wrap));
+    if (carry)
+        atomicAdd(d + 1, (unsigned long long)HistSlot::esc_bytes(carry));
 }
 
 __global__ __launch_bounds__(BLOCK) void k_hist(HistJobs J, const uint32_t *meta,
                                                 uint64_t n, uint64_t per_block,
-                                                uint64_t *partial)
+                                                uint32_t *partial, uint64_t *g_ctr,
+                                                uint64_t *g_id, uint32_t id_dir)
 {
     const HistJob jb = J.j[blockIdx.y];
-    unsigned long long *s = reinterpret_cast<unsigned long long *>(cfc_smem);
+    const HistLds L = hist_lds();
+    uint32_t *s = L.s;
+    for (uint32_t j = threadIdx.x; j < HIST_ESC_SLOTS; j += BLOCK) {
+        L.ek[j] = NONE;
+        L.ec[j] = 0;
+        L.ew[j] = 0;
+    }
     for (uint32_t j = threadIdx.x; j < jb.cnt; j += BLOCK)
         s[j] = 0;
     __syncthreads();
@@ -944,25 +1028,47 @@ __global__ __launch_bounds__(BLOCK) void k_hist(HistJobs J, const uint32_t *meta
     for (uint64_t i = i0; i < end4; i += 4 * BLOCK) {
         uint4 w2, m2;
         load(i + 8 * BLOCK, w2, m2);
-        hist_add(s, jb, w0.x, m0.x);
-        hist_add(s, jb, w0.y, m0.y);
-        hist_add(s, jb, w0.z, m0.z);
-        hist_add(s, jb, w0.w, m0.w);
+        // the four atomics issue back to back; their returns are looked at
+        // once, after the last
+        const HistAdd a0 = hist_add(s, jb, w0.x, m0.x);
+        const HistAdd a1 = hist_add(s, jb, w0.y, m0.y);
+        const HistAdd a2 = hist_add(s, jb, w0.z, m0.z);
+        const HistAdd a3 = hist_add(s, jb, w0.w, m0.w);
+        if (hist_spills(a0) | hist_spills(a1) | hist_spills(a2) | hist_spills(a3)) {
+            hist_escape(L, jb, a0, g_ctr, g_id, id_dir);
+            hist_escape(L, jb, a1, g_ctr, g_id, id_dir);
+            hist_escape(L, jb, a2, g_ctr, g_id, id_dir);
+            hist_escape(L, jb, a3, g_ctr, g_id, id_dir);
+        }
         w0 = w1; m0 = m1;
         w1 = w2; m1 = m2;
     }
-    for (uint64_t i = end4 + threadIdx.x; i < end; i += BLOCK)
-        hist_add(s, jb, jb.keys[i], jb.packed ? 0u : meta[i]);
+    for (uint64_t i = end4 + threadIdx.x; i < end; i += BLOCK) {
+        const HistAdd a = hist_add(s, jb, jb.keys[i], jb.packed ? 0u : meta[i]);
+        if (hist_spills(a))
+            hist_escape(L, jb, a, g_ctr, g_id, id_dir);
+    }
     __syncthreads();
-    uint64_t *dst = partial + jb.poff + (uint64_t)blockIdx.x * jb.cnt;
+    uint32_t *dst = partial + jb.poff + (uint64_t)blockIdx.x * jb.cnt;
     for (uint32_t j = threadIdx.x; j < jb.cnt; j += BLOCK)
-        st_nt((uint64_t)s[j], dst + j);
+        st_nt(s[j], dst + j);
+    // the escapes: straight into the counters, one atomic pair per entry
+    for (uint32_t j = threadIdx.x; j < HIST_ESC_SLOTS; j += BLOCK) {
+        const uint32_t r = L.ek[j];
+        if (r == NONE)
+            continue;
+        const uint32_t carries = L.ec[j], wraps = L.ew[j];
+        unsigned long long *d = hist_dst(jb, jb.lo + r, g_ctr, g_id, id_dir);
+        atomicAdd(d, (unsigned long long)HistSlot::esc_packets(carries, wraps));
+        if (carries)
+            atomicAdd(d + 1, (unsigned long long)HistSlot::esc_bytes(carries));
+    }
 }
 
 // blockIdx.y: job, blockIdx.x: 256 keys of it
 // blockIdx.z: a group of REDUCE_ROWS slices
 constexpr uint32_t REDUCE_ROWS = 32;
-__global__ __launch_bounds__(256) void k_hist_reduce(HistJobs J, const uint64_t *partial,
+__global__ __launch_bounds__(256) void k_hist_reduce(HistJobs J, const uint32_t *partial,
                                                      uint32_t nblk, uint64_t *g_ctr,
                                                      uint64_t *g_id, uint32_t id_dir)
 {
@@ -971,20 +1077,22 @@ __global__ __launch_bounds__(256) void k_hist_reduce(HistJobs J, const uint64_t 
     if (j >= jb.cnt)
         return;
     uint64_t pk = 0, by = 0;
-    const uint64_t *p = partial + jb.poff + j;
+    const uint32_t *p = partial + jb.poff + j;
     const uint32_t b0 = blockIdx.z * REDUCE_ROWS, b1 = min(nblk, b0 + REDUCE_ROWS);
     for (uint32_t b = b0; b < b1; b++) {
-        const uint64_t v = ld_nt(p + (uint64_t)b * jb.cnt);
-        pk += v >> 40;
-        by += v & BYTES_MASK;
+        const uint32_t v = ld_nt(p + (uint64_t)b * jb.cnt);
+        pk += HistSlot::packets(v);
+        by += HistSlot::bytes(v);
     }
-    if (!pk)
+    // (a key whose packet fields are zero may still hold bytes: the fields
+    // are what the escapes left, not the counts)
+    if (!(pk | by))
         return;
-    const uint32_t key = jb.lo + j;
-    uint64_t *dst = jb.kind == 0 ? g_ctr + 2ull * key
-                                 : g_id + id_index(id_dir, key >> 1, key & 1);
-    atomicAdd((unsigned long long *)dst, (unsigned long long)pk);
-    atomicAdd((unsigned long long *)dst + 1, (unsigned long long)by);
+    unsigned long long *dst = hist_dst(jb, jb.lo + j, g_ctr, g_id, id_dir);
+    if (pk)
+        atomicAdd(dst, (unsigned long long)pk);
+    if (by)
+        atomicAdd(dst + 1, (unsigned long long)by);
 }
 
 // CONNTRACK_ACCOUNTING: the per-header keys (slot * 2 + dir) of a
@@ -1691,14 +1799,14 @@ void launch_mode(const DevTables &T, const cfc_hdr_v4 &in, const cfc_out &out,
 }
 
 // histogram slices of an n-header batch with `slots` keys in all: one per
-// CU of an MI355X (a slice of at most 2^24 headers, a multiple of 4), fewer
-// when the partial slabs would pass 256 MiB
+// CU of an MI355X (a slice of at most SLICE_MAX headers, a multiple of 4),
+// fewer when the partial slabs (one u32 per slot and slice) would pass 256 MiB
 uint32_t hist_slices(uint64_t n, uint64_t slots)
 {
     if (!n || !slots)
         return 0;
     uint64_t nb = std::min<uint64_t>(256, (n + 4095) / 4096);
-    nb = std::min<uint64_t>(nb, std::max<uint64_t>(1, (256ull << 20) / (8 * slots)));
+    nb = std::min<uint64_t>(nb, std::max<uint64_t>(1, (256ull << 20) / (4 * slots)));
     nb = std::max<uint64_t>(nb, (n + SLICE_MAX - 1) / SLICE_MAX);
     return (uint32_t)std::max<uint64_t>(nb, 1);
 }
@@ -1792,7 +1900,7 @@ WsLayout ws_layout(uint64_t n, const DevTables &T, int mode, bool ct)
     w.partial = off;
     const uint64_t slots = hist_slots(T, mode);
     w.nblk = hist_slices(n, slots);
-    off += 8ull * slots * w.nblk;
+    off += 4ull * slots * w.nblk;
     const uint32_t nbuck = ctp_buckets(T);
     if (ct && T.ct_st && nbuck) {
         const uint64_t per = acc_slice(n);
@@ -2003,9 +2111,9 @@ bool launch_counters(const DevTables &T, const uint32_t *meta, const uint8_t *tf
     }
     if (jobs.empty())
         return sums;
-    uint64_t *partial = reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(ws) + w.partial);
+    uint32_t *partial = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(ws) + w.partial);
     const uint64_t per_block = hist_per_block(n, w.nblk);
-    set_lds_limit((const void *)k_hist, (int)(8 * HIST_RANGE));
+    set_lds_limit((const void *)k_hist, (int)(HIST_ESC_BYTES + 4 * HIST_RANGE));
     const uint32_t id_dir = mode == CFC_MODE_EGRESS ? ID_DIR_EGRESS : ID_DIR_INGRESS;
     for (size_t a = 0; a < jobs.size(); a += HIST_JOBS_MAX) {
         HistJobs J{};
@@ -2015,8 +2123,9 @@ bool launch_counters(const DevTables &T, const uint32_t *meta, const uint8_t *tf
             J.j[k] = jobs[a + k];
             cmax = std::max(cmax, J.j[k].cnt);
         }
-        hipLaunchKernelGGL(k_hist, dim3(w.nblk, nj), dim3(BLOCK), 8ull * cmax, s, J,
-                           meta, n, per_block, partial);
+        hipLaunchKernelGGL(k_hist, dim3(w.nblk, nj), dim3(BLOCK),
+                           HIST_ESC_BYTES + 4ull * cmax, s, J, meta, n, per_block, partial,
+                           g_ctr, C.g_id, id_dir);
         hipLaunchKernelGGL(k_hist_reduce,
                            dim3((cmax + 255) / 256, nj, (w.nblk + REDUCE_ROWS - 1) / REDUCE_ROWS),
                            dim3(256), 0, s, J, partial, w.nblk, g_ctr, C.g_id, id_dir);

@@ -63,9 +63,52 @@ constexpr int LDS_BYTES_MAX = 160 * 1024;
 //            node's identities fill the first ranges; any other identity
 //            is counted by a direct atomic in the classify kernel.
 // NONE (0xFFFFFFFF) = nothing to count.
+//
+// A histogram slot is one u32, {packets: 11 bits | bytes: 21 bits}
+// (HistSlot), so a 160 KiB LDS holds HIST_RANGE = 36864 keys beside the
+// escape table: every identity a packed key can carry takes at most two
+// ranges, and a policy table of up to 36864 entries one.  The thread whose
+// add overflows a field sees it in the value the atomic returns; those
+// escapes are summed per workgroup in a small LDS table (HIST_ESC_SLOTS
+// entries) and added to the counters directly, beside the slabs.
 constexpr uint32_t KEY_NONE = 0xFFFFFFFFu;
-constexpr uint32_t HIST_RANGE = 18432;   // LDS slots per histogram range (144 KiB)
+constexpr uint32_t HIST_RANGE = 36864;   // LDS slots per histogram range (144 KiB)
+constexpr uint32_t HIST_ESC_SLOTS = 1024;                  // escape table entries
+constexpr uint32_t HIST_ESC_BYTES = HIST_ESC_SLOTS * 12;   // {key, carries, wraps}
 constexpr uint32_t PACK_MAX = 0xFFFF;    // packed keys: key < PACK_MAX
+static_assert(4 * HIST_RANGE + HIST_ESC_BYTES <= LDS_BYTES_MAX, "k_hist's LDS");
+
+// The arithmetic of a 32-bit histogram slot, shared by k_hist / k_hist_reduce
+// and the host self-test.  One header adds inc(len) to its key's slot.  The
+// byte field moves only by the len adds, modulo 2^BY; what it spills (carry,
+// 0 or 1: len <= 65535 < 2^BY) lands in the packet field, which so moves by
+// 1 + carry modulo 2^PK and spills wrap (0 or 1) out of the word.  Each
+// overflow is seen by exactly the thread whose add caused it, so with
+// carries and wraps the counts of a (slice, key):
+//   bytes   = by_final + 2^BY * carries
+//   packets = pk_final + 2^PK * wraps - carries
+struct HistSlot {
+    static constexpr uint32_t BY = 21, PK = 32 - BY;
+    static constexpr uint32_t BYMASK = (1u << BY) - 1;
+    static_assert(65535 <= BYMASK, "skb->len fits the byte field");
+    __host__ __device__ static uint32_t inc(uint32_t len) { return (1u << BY) | len; }
+    // what adding inc(len) to a slot that held `old` spilled
+    __host__ __device__ static void spill(uint32_t old, uint32_t len, uint32_t &carry,
+                                          uint32_t &wrap)
+    {
+        carry = ((old & BYMASK) + len) >> BY;
+        wrap = ((old >> BY) + 1 + carry) >> PK;
+    }
+    __host__ __device__ static uint64_t packets(uint32_t slot) { return slot >> BY; }
+    __host__ __device__ static uint64_t bytes(uint32_t slot) { return slot & BYMASK; }
+    // what the escapes add to the slots' fields (packets as a two's
+    // complement u64: it may be negative)
+    __host__ __device__ static uint64_t esc_packets(uint64_t carries, uint64_t wraps)
+    {
+        return (wraps << PK) - carries;
+    }
+    __host__ __device__ static uint64_t esc_bytes(uint64_t carries) { return carries << BY; }
+};
 
 // Per-identity forward/drop counters (cfc.h cfc_identity_counters): a block
 // of u64 [dir 2][ID_SLOTS identities][outcome 2][packets, bytes] after the

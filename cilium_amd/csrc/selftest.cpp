@@ -11,6 +11,7 @@
 #include <random>
 #include <vector>
 
+#include "classify.hpp"
 #include "flatten.hpp"
 #include "maps.hpp"
 #include "selfcut.hpp"
@@ -334,6 +335,62 @@ static int map_fuzz(std::mt19937 &gen)
     return bad != 0;
 }
 
+// the 32-bit histogram slot (classify.hpp HistSlot): k_hist's per-header
+// update replayed in order on one slot, its carries and wraps counted as the
+// kernel's escape table does, and the recombined sums against plain u64
+// sums — for lengths that never, always and sometimes overflow the byte
+// field, and add counts around the packet field's 2^11
+static int hist_slot_case(const char *name, const std::vector<uint32_t> &lens)
+{
+    uint32_t slot = 0;
+    uint64_t carries = 0, wraps = 0, packets = 0, bytes = 0;
+    for (uint32_t len : lens) {
+        uint32_t carry, wrap;
+        HistSlot::spill(slot, len, carry, wrap);   // (slot: what the atomic returns)
+        slot += HistSlot::inc(len);
+        carries += carry;
+        wraps += wrap;
+        packets++;
+        bytes += len;
+    }
+    const uint64_t pk = HistSlot::packets(slot) + HistSlot::esc_packets(carries, wraps);
+    const uint64_t by = HistSlot::bytes(slot) + HistSlot::esc_bytes(carries);
+    const bool ok = pk == packets && by == bytes;
+    if (!ok)
+        printf("hist slot %s n=%zu: packets %llu want %llu, bytes %llu want %llu\n", name,
+               lens.size(), (unsigned long long)pk, (unsigned long long)packets,
+               (unsigned long long)by, (unsigned long long)bytes);
+    return !ok;
+}
+static int hist_slot_tests(std::mt19937 &gen)
+{
+    int bad = 0;
+    const uint32_t pick[] = {0, 1, 59, 1500, 65534, 65535};
+    for (size_t n : {(size_t)1, (size_t)2047, (size_t)2048, (size_t)2049, (size_t)100000}) {
+        std::vector<uint32_t> v(n);
+        std::fill(v.begin(), v.end(), 65535u);
+        bad += hist_slot_case("max", v);
+        std::fill(v.begin(), v.end(), 0u);
+        bad += hist_slot_case("zero", v);
+        for (size_t i = 0; i < n; i++)
+            v[i] = (i & 1) ? 65535u : 0u;
+        bad += hist_slot_case("alternating", v);
+        for (size_t i = 0; i < n; i++)
+            v[i] = gen() & 0xFFFF;
+        bad += hist_slot_case("random", v);
+        for (size_t i = 0; i < n; i++)
+            v[i] = pick[gen() % 6];
+        bad += hist_slot_case("mixed", v);
+    }
+    // the ranges that follow from the slot width: every identity a packed
+    // key can carry has a range, and id_cover has a bit for it
+    bad += ID_RANGES > 32 || id_range_of(ID_PACK_LIMIT - 1) != ID_RANGES - 1 ||
+           2 * ID_RANGE != HIST_RANGE;
+    printf("hist slot u32 {%u | %u}, %u ranges of %u identities     %s\n", HistSlot::PK,
+           HistSlot::BY, ID_RANGES, ID_RANGE, bad ? "FAIL" : "ok");
+    return bad != 0;
+}
+
 int main()
 {
     std::mt19937 gen(12345);
@@ -388,5 +445,6 @@ int main()
     fail |= clear_suffix_kats();
     fail |= map_fuzz(gen);
     fail |= lpm4_tests(gen);
+    fail |= hist_slot_tests(gen);
     return fail;
 }
