@@ -238,16 +238,18 @@ struct cfc_ctx {
     uint64_t n_ct_grow = 0;   // device-side CT table growths (ct_grow)
     // traffic to itself (selfseg.hip, self_cuts): the candidate addresses,
     // the listed headers and their count; segments run before the last; the
-    // last segment of the last cut batch, which its cfc_ct_apply folds
+    // last segment of each cut batch no cfc_ct_apply has folded yet (by the
+    // batch's cfc_out.ct, as nat): where it starts.  A classify writes or
+    // erases the record of its own key only, the batch's apply takes it.
     DevBuf self_addr, self_rows, self_cnt;
     uint64_t n_self_segs = 0;
-    struct {
-        bool valid = false;
-        const void *ct = nullptr, *saddr = nullptr;
+    struct SegRec {
+        const void *saddr = nullptr;
         uint64_t n = 0, off = 0;
         int mode = 0, family = 0;
         uint16_t ep = 0;
-    } seg;
+    };
+    std::map<const void *, SegRec> segs;
     // the IPv6 table's device applies: creates the host lacks, inserts
     // since the last sync, CtLog6 entries
     uint64_t cta_claims6 = 0, cta_ins6 = 0, log6_used = 0;
@@ -2529,7 +2531,10 @@ int classify(cfc_ctx *c, const Hdr *in, const cfc_out *out, int mode,
     (void)hipSetDevice(c->device);
     hipStream_t s = (hipStream_t)stream;
     constexpr bool V6 = std::is_same<Hdr, cfc_hdr_v6>::value;
-    c->seg.valid = false;
+    // these buffers hold a new batch from here on: the record of the one
+    // they held is void (other batches' records stay for their applies)
+    if (out->ct)
+        c->segs.erase((const void *)out->ct);
     std::vector<uint64_t> cuts;
     int rc = self_cuts(c, *in, *out, mode, ep_lxc, s, &cuts);
     if (rc)
@@ -2558,14 +2563,13 @@ int classify(cfc_ctx *c, const Hdr *in, const cfc_out *out, int mode,
         }
         a = b;
     }
-    c->seg.valid = true;
-    c->seg.ct = out->ct;
-    c->seg.saddr = in->saddr;
-    c->seg.n = in->n;
-    c->seg.off = cuts[cuts.size() - 2];
-    c->seg.mode = mode;
-    c->seg.family = V6 ? 6 : 4;
-    c->seg.ep = ep_lxc;
+    cfc_ctx::SegRec &r = c->segs[(const void *)out->ct];
+    r.saddr = in->saddr;
+    r.n = in->n;
+    r.off = cuts[cuts.size() - 2];
+    r.mode = mode;
+    r.family = V6 ? 6 : 4;
+    r.ep = ep_lxc;
     return 0;
 }
 
@@ -4451,15 +4455,20 @@ int ct_apply(cfc_ctx *c, int family, const Hdr *in, const cfc_out *out, int mode
     if (!c || !in || !out || !out->ct || !out->verdict || !out->identity)
         return -EINVAL;
     std::lock_guard<std::recursive_mutex> g(c->mu);
-    if (c->seg.valid && c->seg.ct == (const void *)out->ct && c->seg.saddr == in->saddr &&
-        c->seg.n == in->n && c->seg.mode == mode && c->seg.ep == ep_lxc &&
-        c->seg.family == family) {
+    auto sg = c->segs.find((const void *)out->ct);
+    if (sg != c->segs.end()) {
         // a batch cut for traffic to itself: its segments before the last
-        // were folded by cfc_classify; fold the last
-        c->seg.valid = false;
-        const uint64_t a = c->seg.off;
-        const Hdr si = sub_batch(*in, a, in->n - a);
-        const cfc_out so = sub_out(*out, a, family == 6);
+        // were folded by cfc_classify; fold the last.  The record is the
+        // last classify's into these outputs (any later one wrote or erased
+        // it), so a call that differs from it in any field is not that
+        // batch's apply: folding it whole would fold [0, off) again.
+        const cfc_ctx::SegRec r = sg->second;
+        if (r.saddr != (const void *)in->saddr || r.n != in->n || r.mode != mode ||
+            r.ep != ep_lxc || r.family != family)
+            return -EINVAL;
+        c->segs.erase(sg);
+        const Hdr si = sub_batch(*in, r.off, in->n - r.off);
+        const cfc_out so = sub_out(*out, r.off, family == 6);
         return ct_apply(c, family, &si, &so, mode, ep_lxc, stream);
     }
     auto it = c->nat.find((const void *)out->ct);

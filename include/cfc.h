@@ -362,7 +362,8 @@ typedef struct {
  * batch (conntrack.h:487-494, 725-748): the segments before the last are
  * classified and folded into CT here, in order (synchronising `stream`),
  * and the cfc_ct_apply_* of the same batch folds the last
- * (cfc_stats.ct_self_segments). */
+ * (cfc_stats.ct_self_segments).  Other batches may be classified, and
+ * applied, before that apply (below: "Batches in flight"). */
 int cfc_classify_v4(cfc_ctx *ctx, const cfc_hdr_v4 *in, const cfc_out *out,
                     int mode, uint16_t ep_lxc, void *stream);
 /* The IPv6 chain: bpf_netdev.c handle_ipv6 (:172-275) -> bpf_lxc.c
@@ -400,7 +401,26 @@ int cfc_classify_v6(cfc_ctx *ctx, const cfc_hdr_v6 *in, const cfc_out *out,
  * wait for a commit, or an IPv6 (or, with CFC_OPT_CT_EVICT 0, an IPv4) CT
  * map could pass its max_entries: then on the host.  A table that would
  * pass 3/4 load is rebuilt larger.
- * Synchronises `stream`. */
+ * Synchronises `stream`.
+ *
+ * Batches in flight.  Any number of classified batches may be outstanding
+ * before their applies, and they may be applied in any order, on any
+ * stream: what a cfc_classify_* leaves for "the cfc_ct_apply_* of the same
+ * batch" — a cut batch's last segment, a NAT hop batch — is kept per batch,
+ * matched by cfc_out.ct (and checked against `in`, n, mode, ep_lxc and the
+ * family), and the launch's hit slots are used only while that launch is
+ * the last one and the CT table has not changed since (the apply probes the
+ * table otherwise: the same result).  A cfc_classify_* into the outputs of
+ * an earlier batch discards that batch's pending record: its apply may no
+ * longer be called.  A cut batch's record lives until its apply or the next
+ * classify into the same outputs; an apply with that cfc_out.ct and another
+ * `in`, n, mode, ep_lxc or family returns -EINVAL and folds nothing (folded
+ * whole, the batch's earlier segments would be folded twice).
+ * Each classify sees the CT maps as the applies before it left them, so
+ * with batches in flight the results equal the reference's packet order —
+ * the batches folded one after the other — only for batches that share no
+ * CT key (no flow, and no address pair: a create's ICMP entry holds both);
+ * that much tests/test_gpu_interleave.py pins. */
 int cfc_ct_apply_v4(cfc_ctx *ctx, const cfc_hdr_v4 *in, const cfc_out *out,
                     int mode, uint16_t ep_lxc, void *stream);
 int cfc_ct_apply_v6(cfc_ctx *ctx, const cfc_hdr_v6 *in, const cfc_out *out,
