@@ -218,6 +218,7 @@ struct cfc_ctx {
         int mode = 0;
         uint16_t ep = 0;
         uint32_t m = 0;            // hop rows
+        hipStream_t stream = nullptr;   // of the last work on its buffers
         DevBuf idx, rows, outs, ws;
         cfc_hdr_v4 h4{};
         cfc_hdr_v6 h6{};
@@ -2078,7 +2079,20 @@ int nat_hop(cfc_ctx *c, const DevTables &T, const EgressArgs &ea, const Hdr &in,
         for (auto it = c->nat.begin(); it != c->nat.end();)
             it = it->second.family == 0 && it->first != key ? c->nat.erase(it) : std::next(it);
     }
+    if (!c->nat.count(key)) {
+        // a consumed record's buffers for this batch (a cut egress batch lists
+        // hops segment by segment, each under its own cfc_out.ct): one whose
+        // last work ran on this stream, so the reuse is ordered behind it
+        for (auto it = c->nat.begin(); it != c->nat.end(); ++it)
+            if (it->second.family == 0 && it->second.stream == s) {
+                auto nh = c->nat.extract(it);
+                nh.key() = key;
+                c->nat.insert(std::move(nh));
+                break;
+            }
+    }
     cfc_ctx::NatRec &r = c->nat[key];
+    r.stream = s;
     r.family = V6 ? 6 : 4;
     r.saddr = in.saddr;
     r.n = in.n;
@@ -2122,9 +2136,36 @@ int nat_hop(cfc_ctx *c, const DevTables &T, const EgressArgs &ea, const Hdr &in,
         h.tf = (uint8_t *)(rp + 5 * m4);
         r.h4 = cfc_hdr_v4{h.sa, h.da, h.pt, h.mt, nullptr, h.tf, m, h.hash};
         rc = nat64_gather(in, idx, m, ea.nat_v4, h, s);
+        // the hop rows' service step in packet order, as classify_one's for
+        // an egress batch: a later packet of a flow finds the CT_SERVICE
+        // entry the first one creates, whatever its own skb->hash selects
+        // (the listing launch is through with the shared words and keys)
+        uint32_t nsvo = 0;
+        if (!rc && T.lb4) {
+            const size_t sb = svc_order_tmp_bytes(m);
+            if (c->svo_keys.bytes < 8ull * m || c->svo.bytes < 4ull * m ||
+                c->svo_tmp.bytes < sb) {
+                (void)hipStreamSynchronize(s);
+                if (c->svo_keys.ensure(8ull * m) || c->svo_keys2.ensure(8ull * m) ||
+                    c->svo_tmp.ensure(sb) || c->svo.zeros(4ull * m, s))
+                    return -ENOMEM;
+            }
+            if (!c->svo_cnt.p && c->svo_cnt.zeros(16, s))
+                return -ENOMEM;
+            SvoArgs sa{h.sa, h.da, h.pt, h.mt, h.hash, m, ep_lxc, ea.ct_owner,
+                       (uint64_t *)c->svo_keys.p, (uint64_t *)c->svo_keys2.p,
+                       (uint32_t *)c->svo.p, (uint32_t *)c->svo_cnt.p, c->svo_tmp.p,
+                       c->svo_tmp.bytes};
+            rc = svc_order(T, sa, false, &nsvo, s);
+            if (!rc && nsvo)
+                e2.svo = (const uint32_t *)c->svo.p;
+        }
         if (!rc)
             rc = launch_classify_v4(Th, r.h4, r.o, smode, e2, c->ctr, (uint32_t *)r.ws.p,
                                     c->num_cus, s, nullptr);
+        if ((nsvo || (rc && T.lb4)) && c->svo.p &&   // (the entry words zero again, on every exit)
+            hipMemsetAsync(c->svo.p, 0, 4ull * m, s) != hipSuccess && !rc)
+            rc = -EIO;
     } else {              // NAT46: IPv6 ingress rows
         NatHop6 h{};
         h.sa = (uint4 *)rp;
@@ -2137,14 +2178,26 @@ int nat_hop(cfc_ctx *c, const DevTables &T, const EgressArgs &ea, const Hdr &in,
         r.h6 = cfc_hdr_v6{(const uint8_t *)h.sa, (const uint8_t *)h.da, h.pt, h.mt, h.mk, h.tf,
                           m, nullptr};
         e2.nat_id = h.id;
-        rc = nat46_gather(T, in, out.identity, idx, m, (const uint4 *)c->epoch->ep->nat6.p, h,
-                          s);
+        // an egress batch's hops: the packet as local delivery saw it — with
+        // a load balancer after the service step, whose arrays the launch
+        // left in the workspace (launch_classify_v4)
+        const bool egr = mode == CFC_MODE_EGRESS;
+        cfc_hdr_v4 gin = in;
+        if (egr && (T.lb4 || T.rnat4)) {
+            const WsLayout lw = ws_layout(in.n, T, mode, true);
+            const uint32_t *a = (const uint32_t *)((const char *)c->ws + lw.lb);
+            const uint64_t st = (in.n + 3) & ~3ull;   // (ctr_stride: one u32 per header)
+            gin.saddr = a + 2 * st;   // (LbArgs: tda, tpt, psa, pda, ppt, fl)
+            gin.daddr = a + 3 * st;
+        }
+        rc = nat46_gather(T, gin, egr ? nullptr : out.identity, ea.seclabel, idx, m,
+                          (const uint4 *)c->epoch->ep->nat6.p, h, s);
         if (!rc)
             rc = launch_classify_v6(Th, r.h6, r.o, smode, e2, c->ctr, (uint32_t *)r.ws.p,
                                     c->num_cus, s, nullptr);
     }
     if (!rc)
-        rc = nat_scatter(idx, m, r.o, out, s);
+        rc = nat_scatter(idx, m, r.o, out, !V6 && mode == CFC_MODE_EGRESS, s);
     c->n_nat_hops += m;
     if (rc || !out.ct)
         r.family = 0;   // (no apply follows)
@@ -2187,8 +2240,8 @@ int classify_one(cfc_ctx *c, const Hdr *in, const cfc_out *out, int mode,
     }
     // LXC_NAT46: the kernel lists the headers that take a hop — NAT64 from
     // an IPv6 egress batch of an endpoint with LXC_IPV4, NAT46 from an IPv4
-    // ingress batch while an entry may carry nat46 and an endpoint has an
-    // IPv6 address
+    // batch (ingress, or egress with its local delivery) while an entry may
+    // carry nat46 and an endpoint has an IPv6 address
     bool nat_list = false;
     if constexpr (std::is_same<Hdr, cfc_hdr_v6>::value) {
         if (mode == CFC_MODE_EGRESS) {
@@ -2197,8 +2250,10 @@ int classify_one(cfc_ctx *c, const Hdr *in, const cfc_out *out, int mode,
             nat_list = ea.nat_v4 != 0 && in->n;
         }
     } else {
-        T.nat46 = (mode == CFC_MODE_INGRESS || mode == CFC_MODE_FULL) && E.T.ct4 &&
-                  E.ep->nat6.p && (E.ct->n_nat46 || c->nat46_seen);
+        // (an egress batch: ipv4_policy as the destination's program behind
+        // local delivery)
+        T.nat46 = mode != CFC_MODE_XDP && E.T.ct4 && E.ep->nat6.p &&
+                  (E.ct->n_nat46 || c->nat46_seen);
         nat_list = T.nat46 && in->n;
     }
     if (nat_list) {
@@ -4478,9 +4533,15 @@ int ct_apply(cfc_ctx *c, int family, const Hdr *in, const cfc_out *out, int mode
     cfc_ctx::NatRec &r = it->second;
     r.family = 0;   // (consumed; its buffers stay for the next hop batch)
     hipStream_t s = (hipStream_t)stream;
+    r.stream = s;
     (void)hipSetDevice(c->device);
     const uint32_t *idx = (const uint32_t *)r.idx.p;
-    if (nat_pre(idx, r.m, *out, s))
+    // an IPv4 egress batch's hops (behind local delivery): both nibbles of
+    // the CT byte are IPv4 stages — the egress stage and the destination's
+    // hit — and fold with the batch; the hop's ipv6_policy stage is a third,
+    // the hop batch's alone
+    const bool third = family == 4 && mode == CFC_MODE_EGRESS;
+    if (nat_pre(idx, r.m, *out, third, s))
         return -EIO;
     int rc = ct_apply_one(c, family, in, out, mode, ep_lxc, stream);
     if (!rc) {
@@ -4490,7 +4551,7 @@ int ct_apply(cfc_ctx *c, int family, const Hdr *in, const cfc_out *out, int mode
         c->hop_nat46 = false;
         c->nat46_seen |= family == 6;
     }
-    const int rc2 = nat_scatter(idx, r.m, r.o, *out, s);
+    const int rc2 = nat_scatter(idx, r.m, r.o, *out, third, s);
     return rc ? rc : rc2;
 }
 

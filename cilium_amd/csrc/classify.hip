@@ -478,6 +478,7 @@ __device__ __forceinline__ void r4_verdict(const DevTables &T, const Lds &S,
     h.idw = id_key(T, h.ident, drop1, len);
     h.id_ovf = h.idw == KEY_NONE;
     uint32_t ev2 = 0;
+    bool nat = false;   // (egress) the destination's program takes the NAT46 hop
     if (!EGR) {
         // (branch-free) drop, or redirect_to_proxy for NEW / ESTABLISHED
         // flows (TRACE_TO_PROXY, lxc.h:117), or TRACE_TO_LXC + delivery
@@ -519,7 +520,7 @@ __device__ __forceinline__ void r4_verdict(const DevTables &T, const Lds &S,
             // ct_lookup4 in the destination's CT maps
             uint32_t dp2 = h.dport;
             CtResult c2{CT_NEW, NONE, 0};
-            bool fresh = false;
+            bool fresh = false, hop = false;
             if (CT) {
                 const uint32_t own2 = ct_owner_word(h.rec.w & 0xFFFF,
                                                     (h.rec.w & LXC_CT_LOCAL) != 0);
@@ -565,7 +566,15 @@ __device__ __forceinline__ void r4_verdict(const DevTables &T, const Lds &S,
                 h.ct_k2 = c2.slot != NONE ? ct_acct_key(c2.slot, CT_INGRESS)
                           : c2.res == CT_NEW ? ck_miss4(h.psa, h.da, proto, h.pt, CT_INGRESS, own2)
                                              : NONE;
-                if (LB && c2.res == CT_REPLY) {   // bpf_lxc.c:946-955, packet only
+                // LXC_NAT46 behind local delivery: the destination's
+                // ipv4_policy hit an entry with nat46 (conntrack.h:241-244)
+                // and leaves for NAT46 and ipv6_policy (bpf_lxc.c:939-944,
+                // :1098-1110) as behind from-netdev (r3_identity): that hop
+                // decides (nat.hip); here the hit alone counts.  (A fresh
+                // hit is this header's own plain IPv4 create: no nat46.)
+                hop = T.nat46 && c2.slot != NONE && (h.rec.w & LXC_HAS6) &&
+                      (T.ct_st[c2.slot].tm.flags & CTT_NAT46);
+                if (LB && c2.res == CT_REPLY && !hop) {   // bpf_lxc.c:946-955, packet only
                     const uint4 lw = fresh ? make_uint4((h.lbfl >> 16) | (h.lbfl & LBF_LOOP) << 14,
                                                         0, 0, 0)
                                            : (T.ct4_lb ? ld16(T.ct4_lb + c2.slot)
@@ -577,15 +586,22 @@ __device__ __forceinline__ void r4_verdict(const DevTables &T, const Lds &S,
                 }
             }
             const bool reply2 = CT && c2.res >= CT_REPLY;
-            const PolicyResult pw = policy_access(T, S, h.rec.y, h.rec.z,
-                                                  E.seclabel, dp2, proto,
-                                                  0, frag);
+            // (a hop header: no policy, metric, trace or identity event of
+            // the destination's IPv4 program; the hop batch has them)
+            const PolicyResult pw = hop ? PolicyResult{0, NONE}
+                                        : policy_access(T, S, h.rec.y, h.rec.z,
+                                                        E.seclabel, dp2, proto,
+                                                        0, frag);
             const int w = pw.verdict;
             ctr1 = pw.ctr;
             if (CT)
                 ctb |= ((uint32_t)c2.res | CTO_DONE |
                         ((c2.res == CT_NEW && (w >= 0 || reply2)) ? CTO_CREATE : 0u)) << 4;
-            if (w < 0 && !reply2) {
+            if (hop) {
+                nat = true;
+                act = TC_ACT_OK;
+                ver = 0;
+            } else if (w < 0 && !reply2) {
                 act = TC_ACT_SHOT;
                 ver = DROP_POLICY;
                 met1 = mkey<MODE>(DROP_POLICY, METRIC_INGRESS);
@@ -611,6 +627,8 @@ __device__ __forceinline__ void r4_verdict(const DevTables &T, const Lds &S,
         }
     }
     h.ev2 = ev2;
+    if (EGR)
+        h.nat = nat;
     h.evw = evw;
     h.act = act;
     h.ver = ver;
@@ -834,7 +852,7 @@ __global__ __launch_bounds__(BLOCK, WAVES_PER_SIMD) void k_classify_v4(
                     E.wprobe[(start + w0) >> 6] = pb;
                 }
             }
-            if (!EGR && MODE != CFC_MODE_XDP && E.nat_idx)   // (uniform)
+            if (MODE != CFC_MODE_XDP && E.nat_idx)   // (uniform)
                 list_append(E.nat_idx, E.nat_cnt, h[u].nat && h[u].valid, (uint32_t)start + i);
             if (MODE != CFC_MODE_XDP && h[u].valid && h[u].id_ovf && h[u].need_pol)
                 id_count(C, id_dir, h[u].ident, h[u].drop1, len);

@@ -602,16 +602,21 @@ int nat_sort(const uint32_t *in, uint32_t *out, uint32_t m, uint64_t n, void *tm
              size_t tmp_bytes, hipStream_t s);
 int nat64_gather(const cfc_hdr_v6 &in, const uint32_t *idx, uint32_t m, uint32_t sa4,
                  const NatHop4 &h, hipStream_t s);
+// ident: the listing ingress batch's identities; null: an egress batch's
+// hops (in.saddr / in.daddr the packet's as local delivery saw it, the source
+// identity `seclabel`, no mark)
 int nat46_gather(const DevTables &T, const cfc_hdr_v4 &in, const uint32_t *ident,
-                 const uint32_t *idx, uint32_t m, const uint4 *ep6, const NatHop6 &h,
-                 hipStream_t s);
+                 uint32_t seclabel, const uint32_t *idx, uint32_t m, const uint4 *ep6,
+                 const NatHop6 &h, hipStream_t s);
 // the hop batch's outputs (sub) into the header's (out); sub.ct loses the
-// hop's second stage
+// hop's second stage.  third: an egress batch's hop — out.ct and
+// out.identity stay (the hop's CT stage is a third one)
 int nat_scatter(const uint32_t *idx, uint32_t m, const cfc_out &sub, const cfc_out &out,
-                hipStream_t s);
-// before the apply of the headers' own family: verdict 0, CT bits 4-7 and
-// the event word cleared (nat_scatter restores them after the hop's apply)
-int nat_pre(const uint32_t *idx, uint32_t m, const cfc_out &out, hipStream_t s);
+                bool third, hipStream_t s);
+// before the apply of the headers' own family: verdict 0, CT bits 4-7 (not
+// with third: they are that family's too) and the event word cleared
+// (nat_scatter restores them after the hop's apply)
+int nat_pre(const uint32_t *idx, uint32_t m, const cfc_out &out, bool third, hipStream_t s);
 
 // dst[i] += src[i] for n u64 (counter import)
 int launch_add_u64(uint64_t *dst, const uint64_t *src, uint64_t n,

@@ -22,6 +22,13 @@
 // hop's verdict, identity, action and event are the header's, its CT stage
 // the header's CT byte bits 4-7.  cfc_ct_apply folds the header's own stage
 // with its family's batch and the hop batch into the other family's maps.
+//
+// An IPv4 egress batch lists NAT46 hops too: ipv4_policy runs as the
+// destination's program behind local delivery (l3.h:103-131) and leaves for
+// the hop the same way.  There the header's CT byte is full — the egress
+// stage and the destination's hit, both IPv4 — so the hop's ipv6_policy
+// lookup is a third stage that stays in the hop batch, and the identity
+// output stays the destination identity.
 #include <hipcub/hipcub.hpp>
 
 #include "kern_common.hpp"
@@ -110,11 +117,18 @@ __global__ __launch_bounds__(256) void k_nat64_gather(cfc_hdr_v6 in, const uint3
     }
 }
 
-// NAT46: hop batch row k <- header idx[k] of the IPv4 ingress batch; the
-// destination endpoint found again by daddr, its LXC_IP from ep6
+// NAT46: hop batch row k <- header idx[k] of the IPv4 batch; the
+// destination endpoint found again by daddr, its LXC_IP from ep6.  An
+// ingress batch: the header's own columns, its mark and the identity the
+// classify gave it.  An egress batch (ident null: the hop behind local
+// delivery, l3.h:103-131): in.saddr / in.daddr are the packet's addresses as
+// local delivery saw them (after the service step), the source identity is
+// the sending endpoint's SECLABEL and no mark skips the proxy
+// (ipv4_local_delivery's tail call carries none).
 __global__ __launch_bounds__(256) void k_nat46_gather(DevTables T, cfc_hdr_v4 in,
-                                                      const uint32_t *ident, const uint32_t *idx,
-                                                      uint32_t m, const uint4 *ep6, NatHop6 h)
+                                                      const uint32_t *ident, uint32_t seclabel,
+                                                      const uint32_t *idx, uint32_t m,
+                                                      const uint4 *ep6, NatHop6 h)
 {
     const uint32_t k = blockIdx.x * 256 + threadIdx.x;
     if (k >= m)
@@ -134,26 +148,31 @@ __global__ __launch_bounds__(256) void k_nat46_gather(DevTables T, cfc_hdr_v4 in
     h.pt[k] = pt;
     h.mt[k] = (proto == 1 ? 58u : proto) | (mt & 0xFF00u) | ((mt >> 16) + 20u) << 16;
     // tc_index carries the skip-proxy mark across the tail calls
-    h.mk[k] = in.mark ? (in.mark[i] & 0xF00u) : 0u;
+    h.mk[k] = ident && in.mark ? (in.mark[i] & 0xF00u) : 0u;
     h.tf[k] = in.tcp_flags ? in.tcp_flags[i] : 0;
-    h.id[k] = ident[i];
+    h.id[k] = ident ? ident[i] : seclabel;
 }
 
 // the hop's results into the header's outputs: verdict, identity, action,
 // event (CFC_NT_NATLEN), and its CT stage as the header's bits 4-7 (the
-// hop's own local delivery — a third stage — is not carried: cleared)
+// hop's own local delivery — a third stage — is not carried: cleared).
+// third: the hop came from an egress batch's local delivery — bits 4-7 keep
+// the destination's ipv4_policy lookup (the hop's stage is a third one, the
+// hop batch's alone) and the identity stays the destination identity the
+// egress program resolved.
 __global__ __launch_bounds__(256) void k_nat_scatter(const uint32_t *idx, uint32_t m, cfc_out sub,
-                                                     cfc_out out)
+                                                     cfc_out out, bool third)
 {
     const uint32_t k = blockIdx.x * 256 + threadIdx.x;
     if (k >= m)
         return;
     const uint32_t i = idx[k];
     out.verdict[i] = sub.verdict[k];
-    out.identity[i] = sub.identity[k];
+    if (!third)
+        out.identity[i] = sub.identity[k];
     if (out.action)
         out.action[i] = sub.action[k];
-    if (out.ct) {
+    if (out.ct && !third) {
         // (the hop batch keeps its own second stage — a NAT64 hop's local
         // delivery, the destination's ipv4_policy lookup: a third CT stage
         // its apply folds — the header's byte has room for the hop's first)
@@ -167,15 +186,19 @@ __global__ __launch_bounds__(256) void k_nat_scatter(const uint32_t *idx, uint32
 }
 
 // before the apply of the header's own family: its stage alone — allowed
-// (it led to the hop), no second stage, no event to re-decide
-__global__ __launch_bounds__(256) void k_nat_pre(const uint32_t *idx, uint32_t m, cfc_out out)
+// (it led to the hop), no second stage, no event to re-decide.  third (an
+// egress batch's hop): both nibbles are the IPv4 family's — the egress stage
+// and the destination's hit — and stay
+__global__ __launch_bounds__(256) void k_nat_pre(const uint32_t *idx, uint32_t m, cfc_out out,
+                                                 bool third)
 {
     const uint32_t k = blockIdx.x * 256 + threadIdx.x;
     if (k >= m)
         return;
     const uint32_t i = idx[k];
     out.verdict[i] = 0;
-    out.ct[i] &= 0x0F;
+    if (!third)
+        out.ct[i] &= 0x0F;
     if (out.notify)
         out.notify[i] = 0;
 }
@@ -212,28 +235,29 @@ int nat64_gather(const cfc_hdr_v6 &in, const uint32_t *idx, uint32_t m, uint32_t
 }
 
 int nat46_gather(const DevTables &T, const cfc_hdr_v4 &in, const uint32_t *ident,
-                 const uint32_t *idx, uint32_t m, const uint4 *ep6, const NatHop6 &h,
-                 hipStream_t s)
+                 uint32_t seclabel, const uint32_t *idx, uint32_t m, const uint4 *ep6,
+                 const NatHop6 &h, hipStream_t s)
 {
     if (m)
         hipLaunchKernelGGL(k_nat46_gather, dim3((m + 255) / 256), dim3(256), 0, s, T, in, ident,
-                           idx, m, ep6, h);
+                           seclabel, idx, m, ep6, h);
     return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
 int nat_scatter(const uint32_t *idx, uint32_t m, const cfc_out &sub, const cfc_out &out,
-                hipStream_t s)
+                bool third, hipStream_t s)
 {
     if (m)
         hipLaunchKernelGGL(k_nat_scatter, dim3((m + 255) / 256), dim3(256), 0, s, idx, m, sub,
-                           out);
+                           out, third);
     return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
-int nat_pre(const uint32_t *idx, uint32_t m, const cfc_out &out, hipStream_t s)
+int nat_pre(const uint32_t *idx, uint32_t m, const cfc_out &out, bool third, hipStream_t s)
 {
     if (m)
-        hipLaunchKernelGGL(k_nat_pre, dim3((m + 255) / 256), dim3(256), 0, s, idx, m, out);
+        hipLaunchKernelGGL(k_nat_pre, dim3((m + 255) / 256), dim3(256), 0, s, idx, m, out,
+                           third);
     return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 

@@ -1418,3 +1418,92 @@ def headers_nat46(t, ipc4, hist, hist_ok, n, seed=63):
                          mark_host=0, mark_proxy=0, frag=0)
     h = concat([rep, ep_, new])
     return take(h, rng.permutation(len(h)))
+
+
+# ---- NAT46 behind an IPv4 egress batch's local delivery (l3.h:103-131) -------
+
+
+def config_nat_self(seed=69, allow_ports=None):
+    """config_nat's tables, EP_LXC_ID also admitting its own identity (ingress)
+    on the flows' ports and at L3 — or, with allow_ports, on those host-order
+    TCP / UDP ports alone, so that ipv6_policy drops the other replies: the endpoint's NAT64 flows to its own IPv4 address
+    (::ffff:LXC_IPV4) are delivered to itself by the IPv4 egress program, and
+    so are their IPv4 replies LXC_IPV4 -> LXC_IPV4, whose destination-side
+    ipv4_policy finds the flow's nat46 entry and leaves for NAT46 and
+    ipv6_policy (bpf_lxc.c:939-944, :1098-1110).  -> (tables, IPv4 ipcache
+    rows)"""
+    t, ipc4 = config_nat(seed)
+    sec = int(t.seclabel[EP_LXC_ID])
+    if allow_ports is None:
+        add = np.zeros(4, POLICY_DT)
+        add["dport"] = htons(np.array([80, 53, 443, 0]))
+        add["proto"] = [IPPROTO_TCP, IPPROTO_UDP, IPPROTO_TCP, 0]
+    else:
+        ports = np.asarray(list(allow_ports))
+        add = np.zeros(3 + 2 * len(ports), POLICY_DT)
+        add["dport"] = htons(np.concatenate([[80, 53, 443], np.tile(ports, 2)]))
+        add["proto"] = np.concatenate([[IPPROTO_TCP, IPPROTO_UDP, IPPROTO_TCP],
+                                       np.repeat([IPPROTO_TCP, IPPROTO_UDP], len(ports))])
+    add["identity"] = sec
+    t.policy[EP_LXC_ID] = np.concatenate([t.policy[EP_LXC_ID], add])
+    return t, ipc4
+
+
+def nat64_self_flows(rng, ipc4, n, sport_base):
+    """nat64_flows, every one to the endpoint's own IPv4 address"""
+    h = nat64_flows(rng, ipc4, n, sport_base)
+    h.daddr = v4_mapped(np.full(n, LXC_IPV4, np.uint32))
+    return h
+
+
+def headers_nat46_self(t, ipc4, hist, hist_ok, seed=69, err_frac=0.1, plain_frac=0.2,
+                       errors=True):
+    """An IPv4 egress stream of EP_LXC_ID: the replies LXC_IPV4 -> LXC_IPV4 of
+    the history's forwarded self flows (hist: nat64_self_flows, hist_ok: the
+    forwarded ones) — SYN-ACK, then ACK and data for some, in order — ICMP
+    errors the endpoint sends itself about them (every icmp4_to_icmp6 case;
+    errors=False: none, and the self-cut rule then cuts the batch rarely),
+    and plain IPv4 egress traffic to remote peers beside them"""
+    rng = np.random.default_rng(seed + 500)
+    a4 = np.uint32(LXC_IPV4)
+    ok = np.asarray(hist_ok)
+    parts, pos = [], []
+    at = rng.random(len(ok)) * 0.9
+    for f, p_ in ((0x12, 1.0), (0x10, 0.7), (0x18, 0.5)):
+        sel = np.flatnonzero(rng.random(len(ok)) < p_)
+        src = take(hist, ok[sel])
+        k = len(sel)
+        # (an ICMPv6 echo request's reply: ICMP echo reply, type 0, same id)
+        icmp = src.proto == IPPROTO_ICMPV6
+        rep = Headers(4, np.full(k, a4, np.uint32), np.full(k, a4, np.uint32),
+                      np.where(icmp, 0, src.dport).astype(np.uint16),
+                      np.where(icmp, src.dport, src.sport).astype(np.uint16),
+                      np.where(icmp, IPPROTO_ICMP, src.proto).astype(np.uint8),
+                      np.zeros(k, np.uint8), rng.integers(60, 1500, size=k).astype(np.uint16),
+                      np.zeros(k, np.uint32),
+                      np.where(src.proto == IPPROTO_TCP, f, 0).astype(np.uint8))
+        parts.append(rep)
+        pos.append(at[sel])
+        at = at + rng.random(len(ok)) * 0.03
+    n_rep = sum(len(p) for p in parts)
+    if errors:
+        k = int(n_rep * err_frac)
+        err = take(parts[0], rng.integers(0, len(parts[0]), size=k))
+        tc = np.array([[3, 0], [3, 1], [3, 3], [3, 4], [3, 9], [3, 13], [11, 0], [12, 0], [5, 0]],
+                      np.uint16)
+        pick = tc[rng.integers(0, len(tc), size=k)]
+        err.proto[:] = IPPROTO_ICMP
+        err.sport[:] = (pick[:, 0] | pick[:, 1] << 8).astype(np.uint16)
+        err.dport[:] = 0
+        err.tcpflags = np.zeros(k, np.uint8)
+        parts.append(err)
+        pos.append(rng.random(k))
+    plain = gen_headers_v4(rng, int(n_rep * plain_frac), ipc4, local_v4_addrs(t)[:1],
+                           local_frac=0.0, mark_host=0, mark_proxy=0, frag=0,
+                           src_fixed=LXC_IPV4)
+    parts.append(plain)
+    pos.append(rng.random(len(plain)))
+    h = concat(parts)
+    h = take(h, np.argsort(np.concatenate(pos), kind="stable"))
+    h.hash = None
+    return h

@@ -285,7 +285,20 @@ typedef struct {
  *            endpoint's IPv4 egress path, bpf_lxc.c:353-360, 1070-1083; an
  *            IPv4 ingress header whose CT entry carries nat46 re-runs as IPv6
  *            through ipv6_policy, bpf_lxc.c:939-944, 1098-1110 — its verdict,
- *            identity, action and event are the hop's).  Feed it to
+ *            identity, action and event are the hop's).  Which lookup bits
+ *            4-7 hold, by batch: IPv4 / IPv6 ingress or full — none, or the
+ *            NAT46 hop's ct_lookup6; IPv6 egress — the destination's
+ *            ipv6_policy lookup after local delivery, or the NAT64 hop's
+ *            IPv4 egress lookup; IPv4 egress — the destination's ipv4_policy
+ *            lookup after local delivery, always.  That ipv4_policy leaves for
+ *            the NAT46 hop too when its lookup hit an entry with nat46 (a
+ *            local NAT64 flow's IPv4 reply): bits 4-7 then stay that hit
+ *            (never a create), the verdict, action and event are the hop's,
+ *            the identity stays the destination identity, and the hop's own
+ *            ct_lookup6 / ct_create6 is a third stage no bit of this byte
+ *            shows — like the destination's ipv4_policy behind a NAT64 hop,
+ *            it is kept with the hop batch and only cfc_ct_apply sees it.
+ *            Feed the byte to
  *            cfc_ct_apply_v4/v6 of the same batch (cfc_classify's outputs
  *            untouched in between) to fold creates, deletes and closing flags
  *            into the CT maps, the hop's into the other family's. */
