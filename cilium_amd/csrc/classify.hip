@@ -54,6 +54,7 @@
 //   xdp       bpf_xdp.c:88-121
 //   metrics   bpf/lib/metrics.h:43-61
 #include <algorithm>
+#include <cstdlib>
 #include <mutex>
 #include <set>
 #include <tuple>
@@ -1882,9 +1883,13 @@ int launch_add_u64(uint64_t *dst, const uint64_t *src, uint64_t n,
 }
 
 // key buckets of the CT accounting partition (0: too many keys, the
-// per-slice kernel k_ct_count counts instead)
+// per-slice kernel k_ct_count counts instead; CFC_ACC_PER_SLICE, read per
+// call, selects that kernel for any table — the launch then keeps no
+// plain-hit summaries and its apply takes the dense passes)
 uint32_t ctp_buckets(const DevTables &T)
 {
+    if (getenv("CFC_ACC_PER_SLICE"))
+        return 0;
     const uint64_t slots = (T.ct4 ? T.ct4_mask + 1ull : 0) + (T.ct6 ? T.ct6_mask + 1ull : 0);
     const uint64_t nb = (2 * slots + CTP_BUCKET - 1) / CTP_BUCKET;
     return nb <= CTP_MAX_BUCKETS ? (uint32_t)nb : 0u;
