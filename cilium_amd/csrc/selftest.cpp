@@ -391,8 +391,53 @@ static int hist_slot_tests(std::mt19937 &gen)
     return bad != 0;
 }
 
-int main()
+// known answers of the layout.h hashes, one `kat <name> <inputs> <value>`
+// line each (hex): what a restatement elsewhere (tests/lookup_edges.py, which
+// places keys by them) is compared with
+static void hash_kats()
 {
+    const uint32_t V[] = {0u, 0xFFFFFFFFu, 1u, 0x0100000Au, 0x9E3779B9u, 0x80000000u, 0x1010u};
+    const uint32_t MASKS[] = {0u, 7u, 511u, 0xFFFFu, 0xFFFFFFFFu};
+    for (uint32_t a : V) {
+        printf("kat fmix32 %x %x\n", a, fmix32(a));
+        printf("kat bloom_bits %x %x\n", a, bloom_bits(a));
+        printf("kat pol_bloom_salt %x %x\n", a, pol_bloom_salt(a));
+        printf("kat pf_bloom_hash %x %x\n", a, pf_bloom_hash(a));
+        printf("kat l6_bloom_bits %x %llx\n", a, (unsigned long long)l6_bloom_bits(a));
+        for (uint32_t m : MASKS) {
+            printf("kat hash32 %x %x %x\n", a, m, hash32(a, m));
+            printf("kat pol_slot %x %x %x\n", a, m, pol_slot(a, m));
+        }
+        for (uint32_t b : V) {
+            printf("kat pol_key_pre %x %x %x\n", a, b, pol_key_pre(a, b));
+            printf("kat pol_bloom_hash %x %x %x\n", a, b, pol_bloom_hash(a, b));
+        }
+    }
+    for (uint32_t len : {0u, 1u, 31u, 32u, 33u, 63u, 64u, 65u, 95u, 96u, 97u, 127u, 128u})
+        for (int i = 0; i < 4; i++)
+            printf("kat l6_word_mask %x %x %x\n", len, (uint32_t)i, l6_word_mask(len, i));
+    const uint32_t W[][4] = {{0, 0, 0, 0},
+                             {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu},
+                             {0x20010db8u, 0x00050000u, 0, 1},
+                             {0xbeef0000u, 0, 0x00000001u, 0x016582bcu},
+                             {1, 2, 3, 4}};
+    for (const auto &w : W) {
+        for (uint32_t tag : {0u, 1u, 64u, 65u, 128u, 0x200u, 0xFFFFFFFFu})
+            printf("kat l6_hash %x %x %x %x %x %x\n", w[0], w[1], w[2], w[3], tag,
+                   l6_hash(w[0], w[1], w[2], w[3], tag));
+        for (uint32_t sel : {1u, 32u, 33u, 48u, 64u, 65u, 127u, 128u})
+            printf("kat l6_group_hash %x %x %x %x %x %x\n", w[0], w[1], w[2], w[3], sel,
+                   l6_group_hash(w, sel));
+        printf("kat pf6_bloom_hash %x %x %x %x %x\n", w[0], w[1], w[2], w[3],
+               pf6_bloom_hash(w[0], w[1], w[2], w[3]));
+    }
+}
+
+int main(int argc, char **argv)
+{
+    hash_kats();
+    if (argc > 1 && !strcmp(argv[1], "kat"))   // the known answers alone
+        return 0;
     std::mt19937 gen(12345);
     auto rng = [&gen]() -> uint32_t { return (uint32_t)gen(); };
     int fail = 0;
