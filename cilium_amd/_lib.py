@@ -32,6 +32,8 @@ EXPORTS = (
     "cfc_set_node_config", "cfc_get_node_config", "cfc_identity_counters",
     "cfc_set_clock", "cfc_monitor_events_v4", "cfc_monitor_events_v6",
     "cfc_map_dump", "cfc_ct_gc",
+    "cfc_proxy_entries_v4", "cfc_proxy_entries_v6",
+    "cfc_proxy_apply_v4", "cfc_proxy_apply_v6",
 )
 # CT byte (cfc_out.ct): per stage (bits 0-3, then 4-7 for the destination's
 # ingress lookup after egress local delivery)
@@ -135,6 +137,13 @@ class IdentityCount(ctypes.Structure):
 IDENTITY_OUT_OF_RANGE = 0xFFFFFFFF
 
 
+class ProxyStats(ctypes.Structure):
+    """cfc_proxy_stats (cfc_proxy_apply_v4/v6)"""
+    _fields_ = [("redirects", ctypes.c_uint64), ("entries", ctypes.c_uint64),
+                ("created", ctypes.c_uint64), ("updated", ctypes.c_uint64),
+                ("failed", ctypes.c_uint64)]
+
+
 class Timing(ctypes.Structure):
     _fields_ = [("launches", ctypes.c_uint64), ("classify_ms", ctypes.c_double),
                 ("count_ms", ctypes.c_double), ("launches_v6", ctypes.c_uint64),
@@ -183,6 +192,12 @@ def lib():
               L.cfc_monitor_events_v4, L.cfc_monitor_events_v6):
         f.argtypes = [vp, vp, ctypes.POINTER(Out), i32, ctypes.c_uint16, vp, vp,
                       u64, vp, vp]
+    for f in (L.cfc_proxy_entries_v4, L.cfc_proxy_entries_v6):
+        f.argtypes = [vp, vp, ctypes.POINTER(Out), i32, ctypes.c_uint16, vp, vp,
+                      u64, vp, vp]
+    for f in (L.cfc_proxy_apply_v4, L.cfc_proxy_apply_v6):
+        f.argtypes = [vp, vp, ctypes.POINTER(Out), i32, ctypes.c_uint16,
+                      ctypes.POINTER(ProxyStats), vp]
     L.cfc_counters_device.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(u64)]
     L.cfc_counters_sync.argtypes = [vp, vp]
     L.cfc_counters_clear.argtypes = [vp, vp]

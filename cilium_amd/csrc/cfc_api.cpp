@@ -282,6 +282,14 @@ struct cfc_ctx {
     hipStream_t nt_stream = nullptr;
     bool nt_pending = false;
 
+    // cfc_proxy_entries / cfc_proxy_apply (proxymap.hip): redirect and record
+    // counts, the key table, the winner bitmap, group offsets, the apply's
+    // records; the event after the last launch that used them
+    DevBuf px_cnt, px_own, px_last, px_bm, px_blk, px_rec;
+    hipEvent_t px_done = nullptr;
+    hipStream_t px_stream = nullptr;
+    bool px_pending = false;
+
     // CFC_OPT_TIMING: events of the launches since the last collect
     bool timing = false;
     std::vector<LaunchTiming> tpool;
@@ -1666,6 +1674,9 @@ bool role_geometry_ok(Role r, uint32_t type, uint32_t ks, uint32_t vs)
     case ROLE_CT6: return (type == MT_LRU_HASH || type == MT_HASH) && ks == 38 && vs == 56;
     case ROLE_LB4_SVC: return type == MT_HASH && ks == 8 && vs == 12;     // lbmap/ipv4.go:27
     case ROLE_LB4_RNAT: return type == MT_HASH && ks == 2 && vs == 6;     // :43
+    // struct proxy4_tbl_key / _value, proxy6_tbl_key / _value (common.h:478-508)
+    case ROLE_PROXY4: return type == MT_HASH && ks == 10 && vs == 16;
+    case ROLE_PROXY6: return type == MT_HASH && ks == 22 && vs == 28;
     default: return true;
     }
 }
@@ -1737,6 +1748,7 @@ int cfc_open(int device, cfc_ctx **out)
             c->num_cus = p.multiProcessorCount;
         (void)hipEventCreateWithFlags(&c->last_done, hipEventDisableTiming);
         (void)hipEventCreateWithFlags(&c->nt_done, hipEventDisableTiming);
+        (void)hipEventCreateWithFlags(&c->px_done, hipEventDisableTiming);
     }
     // the datapath owns cilium_metrics (bpf/lib/maps.h:35-41)
     auto m = std::make_unique<Map>();
@@ -1778,6 +1790,8 @@ void cfc_close(cfc_ctx *c)
         (void)hipHostFree(c->pend_cnt);
     if (c->nt_done)
         (void)hipEventDestroy(c->nt_done);
+    if (c->px_done)
+        (void)hipEventDestroy(c->px_done);
     delete c;
 }
 
@@ -2751,6 +2765,190 @@ int cfc_monitor_events_v6(cfc_ctx *c, const cfc_hdr_v6 *in, const cfc_out *out,
 {
     return drop_notify(c, in, out, mode, ep_lxc, (cfc_drop_notify *)rec, hdr_index,
                        cap, count, stream, 6, 1);
+}
+
+}  // extern "C"
+
+namespace {
+
+// cfc_proxy_entries_v4/v6 (st == nullptr) and cfc_proxy_apply_v4/v6
+template <class Hdr>
+int proxy_entries(cfc_ctx *c, const Hdr *in, const cfc_out *out, int mode, uint16_t ep_lxc,
+                  void *rec, uint64_t *hdr_index, uint64_t cap, uint64_t *count,
+                  cfc_proxy_stats *st, void *stream, int family)
+{
+    const bool apply = st != nullptr;
+    if (!c || !in || !out || (!apply && (!count || (cap && !rec))))
+        return -EINVAL;
+    if (reinterpret_cast<uintptr_t>(rec) & 15)
+        return -EINVAL;   // records are written as 16-byte stores (cfc.h)
+    if (mode < CFC_MODE_INGRESS || mode > CFC_MODE_FULL)
+        return -EINVAL;
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    if (c->device == CFC_DEVICE_NONE)
+        return -ENODEV;
+    Map *pm = nullptr;
+    bool lb = false;
+    for (auto &kv : c->maps) {
+        if (kv.second->role == (family == 6 ? ROLE_PROXY6 : ROLE_PROXY4))
+            pm = kv.second.get();
+        if (kv.second->role == (family == 6 ? ROLE_LB6_SVC : ROLE_LB4_SVC))
+            lb = lb || !kv.second->kv.empty();
+    }
+    if (!pm)
+        return -ENOENT;
+    const bool egress = mode == CFC_MODE_EGRESS;
+    if (in->n && (!out->verdict || !in->saddr || !in->daddr || !in->ports || !in->meta ||
+                  (egress ? !out->ct : !out->identity)))
+        return -EINVAL;
+    // a service-translated batch's orig_dip is the packet's, not the header's
+    if (in->n && egress && lb && (!out->pkt_saddr || !out->pkt_daddr || !out->pkt_ports))
+        return -EINVAL;
+    (void)hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (apply)
+        *st = cfc_proxy_stats{};
+    // the workspace is shared: order this call after the previous one
+    if (c->px_pending && c->px_stream != s)
+        (void)hipStreamWaitEvent(s, c->px_done, 0);
+    if (int rc = c->px_cnt.ensure(16))
+        return rc;
+    unsigned long long *cnt = reinterpret_cast<unsigned long long *>(c->px_cnt.p);
+    if (apply)
+        count = reinterpret_cast<uint64_t *>(cnt + 1);
+    if (hipMemsetAsync(cnt, 0, 16, s) != hipSuccess)
+        return -EIO;
+    ProxyArgs a{};
+    a.verdict = out->verdict;
+    a.identity = out->identity;
+    a.ct = out->ct;
+    a.saddr = reinterpret_cast<const uint32_t *>(in->saddr);
+    a.daddr = reinterpret_cast<const uint32_t *>(in->daddr);
+    a.ports = in->ports;
+    a.meta = in->meta;
+    if (egress && out->pkt_saddr && out->pkt_daddr && out->pkt_ports) {
+        a.pkt_saddr = out->pkt_saddr;
+        a.pkt_daddr = out->pkt_daddr;
+        a.pkt_ports = out->pkt_ports;
+    }
+    a.n = in->n;
+    a.egress = egress;
+    // SECLABEL as the batch was classified
+    a.own_seclabel = c->epoch ? c->epoch->ep->seclabel[ep_lxc] : c->seclabel[ep_lxc];
+    a.lifetime = c->now + 720u;   // PROXY_DEFAULT_LIFETIME (common.h:466)
+    a.predup = getenv("CFC_PROXY_NO_PREDUP") ? 0 : 1;
+    a.rec = rec;
+    a.hdr_index = hdr_index;
+    a.cap = cap;
+    a.count = count;
+    int rc = launch_proxy_count(a, cnt, s);
+    if (rc)
+        return rc;
+    unsigned long long redirects = 0;
+    if (hipMemcpyAsync(&redirects, cnt, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return -EIO;
+    if (apply)
+        st->redirects = redirects;
+    if (!redirects)   // no record (*count, when the caller's, still to be written)
+        return apply || hipMemsetAsync(count, 0, 8, s) == hipSuccess ? 0 : -EIO;
+    // a power of two at least twice the redirects: at most half full
+    uint64_t slots = 1024;
+    while (slots < 2 * (uint64_t)redirects)
+        slots <<= 1;
+    const uint64_t groups = proxy_groups(in->n);
+    if ((rc = c->px_own.ensure(slots * 8)) || (rc = c->px_last.ensure(slots * 4)) ||
+        (rc = c->px_bm.ensure(proxy_bitmap_bytes(in->n))) ||
+        (rc = c->px_blk.ensure((groups + 1) * 8)))
+        return rc;
+    ProxyWs w{};
+    w.own = reinterpret_cast<unsigned long long *>(c->px_own.p);
+    w.last = reinterpret_cast<uint32_t *>(c->px_last.p);
+    w.mask = (uint32_t)(slots - 1);
+    w.bitmap = reinterpret_cast<uint64_t *>(c->px_bm.p);
+    w.blk = reinterpret_cast<uint64_t *>(c->px_blk.p);
+    if (hipMemsetAsync(w.own, 0, slots * 8, s) != hipSuccess ||
+        hipMemsetAsync(w.last, 0, slots * 4, s) != hipSuccess ||
+        hipMemsetAsync(w.bitmap, 0, proxy_bitmap_bytes(in->n), s) != hipSuccess)
+        return -EIO;
+    if ((rc = launch_proxy_mark(family, a, w, s)))
+        return rc;
+    const size_t rsz = family == 6 ? sizeof(cfc_proxy6_entry) : sizeof(cfc_proxy4_entry);
+    uint64_t entries = 0;
+    if (apply) {
+        if (hipMemcpyAsync(&entries, count, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess)
+            return -EIO;
+        if ((rc = c->px_rec.ensure(entries * rsz)))
+            return rc;
+        a.rec = c->px_rec.p;
+        a.cap = entries;
+    }
+    if ((rc = launch_proxy_write(family, a, w, s)))
+        return rc;
+    (void)hipEventRecord(c->px_done, s);
+    c->px_stream = s;
+    c->px_pending = true;
+    if (!apply)
+        return 0;
+    std::vector<uint8_t> host(entries * rsz);
+    if (hipMemcpyAsync(host.data(), a.rec, host.size(), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return -EIO;
+    c->px_pending = false;
+    st->entries = entries;
+    const size_t voff = family == 6 ? offsetof(cfc_proxy6_entry, value)
+                                    : offsetof(cfc_proxy4_entry, value);
+    for (uint64_t k = 0; k < entries; k++) {
+        const uint8_t *r = host.data() + k * rsz;
+        const bool held = pm->kv.count(std::string((const char *)r, pm->ksz)) != 0;
+        const int urc = pm->update(r, r + voff, CFC_ANY);
+        if (urc == -E2BIG)
+            st->failed++;   // the reference: DROP_PROXYMAP_CREATE_FAILED
+        else if (urc)
+            return urc;
+        else if (held)
+            st->updated++;
+        else
+            st->created++;
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cfc_proxy_entries_v4(cfc_ctx *c, const cfc_hdr_v4 *in, const cfc_out *out, int mode,
+                         uint16_t ep_lxc, cfc_proxy4_entry *rec, uint64_t *hdr_index,
+                         uint64_t cap, uint64_t *count, void *stream)
+{
+    return proxy_entries(c, in, out, mode, ep_lxc, rec, hdr_index, cap, count, nullptr,
+                         stream, 4);
+}
+
+int cfc_proxy_entries_v6(cfc_ctx *c, const cfc_hdr_v6 *in, const cfc_out *out, int mode,
+                         uint16_t ep_lxc, cfc_proxy6_entry *rec, uint64_t *hdr_index,
+                         uint64_t cap, uint64_t *count, void *stream)
+{
+    return proxy_entries(c, in, out, mode, ep_lxc, rec, hdr_index, cap, count, nullptr,
+                         stream, 6);
+}
+
+int cfc_proxy_apply_v4(cfc_ctx *c, const cfc_hdr_v4 *in, const cfc_out *out, int mode,
+                       uint16_t ep_lxc, cfc_proxy_stats *st, void *stream)
+{
+    return st ? proxy_entries(c, in, out, mode, ep_lxc, nullptr, nullptr, 0, nullptr, st,
+                              stream, 4)
+              : -EINVAL;
+}
+
+int cfc_proxy_apply_v6(cfc_ctx *c, const cfc_hdr_v6 *in, const cfc_out *out, int mode,
+                       uint16_t ep_lxc, cfc_proxy_stats *st, void *stream)
+{
+    return st ? proxy_entries(c, in, out, mode, ep_lxc, nullptr, nullptr, 0, nullptr, st,
+                              stream, 6)
+              : -EINVAL;
 }
 
 int cfc_counters_device(cfc_ctx *c, uint64_t **dev, uint64_t *n)

@@ -672,4 +672,47 @@ struct NotifyArgs {
 size_t drop_notify_workspace_bytes(uint64_t n);
 int launch_drop_notify(const NotifyArgs &a, uint64_t *ws, hipStream_t stream);
 
+// cilium_proxy4/6 entries of one classified batch (proxymap.hip): one record
+// per distinct proxy-map key among the redirected headers (verdict > 0), with
+// the value of the last header that wrote the key, in that header's order.
+struct ProxyArgs {
+    const int32_t *verdict;
+    const uint32_t *identity;   // ingress: the entry's identity (egress: unused)
+    const uint8_t *ct;          // CT bytes (null: every stage CT_NEW, ingress only)
+    const uint32_t *saddr;      // v4: n words; v6: n x 4 words
+    const uint32_t *daddr;
+    const uint32_t *ports;
+    const uint32_t *meta;
+    // the packet as the programs left it (cfc_out.pkt_*), or null = the input
+    const uint32_t *pkt_saddr, *pkt_daddr, *pkt_ports;
+    uint64_t n;
+    int egress;                 // mode == CFC_MODE_EGRESS
+    uint32_t own_seclabel;      // SECLABEL of ep_lxc (egress batches)
+    uint32_t lifetime;          // now + PROXY_DEFAULT_LIFETIME
+    int predup;                 // 1: dedupe in LDS before the global table
+    void *rec;                  // cfc_proxy4_entry / cfc_proxy6_entry
+    uint64_t *hdr_index;        // may be NULL
+    uint64_t cap;
+    uint64_t *count;
+};
+// workspace: the open-addressing table (own: hash << 32 | header index + 1 of
+// the claiming header, last: the key's greatest header index + 1; slots =
+// mask + 1, zeroed), the winner bitmap (one bit per header, proxy_bitmap_bytes,
+// zeroed) and one u64 per group of headers (proxy_groups + 1)
+struct ProxyWs {
+    unsigned long long *own;
+    uint32_t *last;
+    uint32_t mask;
+    uint64_t *bitmap;
+    uint64_t *blk;
+};
+uint64_t proxy_groups(uint64_t n);
+size_t proxy_bitmap_bytes(uint64_t n);
+// headers with verdict > 0 added into *total (device u64, zeroed by the caller)
+int launch_proxy_count(const ProxyArgs &a, unsigned long long *total, hipStream_t stream);
+// mark the keys' last writers, then offsets per group and the total into *count
+int launch_proxy_mark(int family, const ProxyArgs &a, const ProxyWs &w, hipStream_t stream);
+// the records of the winners (after launch_proxy_mark)
+int launch_proxy_write(int family, const ProxyArgs &a, const ProxyWs &w, hipStream_t stream);
+
 }  // namespace cfc

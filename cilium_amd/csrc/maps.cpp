@@ -197,6 +197,10 @@ Role role_for(const std::string &path, int *policy_lxc, int *ct_any)
         return ROLE_LB6_SVC;
     if (b == "cilium_lb6_reverse_nat")
         return ROLE_LB6_RNAT;
+    if (b == "cilium_proxy4")
+        return ROLE_PROXY4;
+    if (b == "cilium_proxy6")
+        return ROLE_PROXY6;
     if (b == "cilium_lxc")
         return ROLE_LXC;
     if (b == "cilium_metrics")

@@ -36,6 +36,8 @@ enum Role {
     ROLE_LB4_RNAT,  // cilium_lb4_reverse_nat
     ROLE_LB6_SVC,   // cilium_lb6_services
     ROLE_LB6_RNAT,  // cilium_lb6_reverse_nat
+    ROLE_PROXY4,    // cilium_proxy4 (host map only: cfc_proxy_apply_v4 writes it)
+    ROLE_PROXY6,    // cilium_proxy6
 };
 
 enum : int { TOUCH_VALUE = 1, TOUCH_INSERT = 2, TOUCH_ERASE = 4 };

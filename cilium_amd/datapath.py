@@ -452,6 +452,44 @@ class Datapath:
         m = min(total, cap)
         return rec[:m], idx[:m], total
 
+    def proxy_entries(self, batch, out: Verdicts, mode=L.MODE_INGRESS, ep_lxc=0,
+                      cap=None, stream=None):
+        """cfc_proxy_entries_v4/v6: the cilium_proxy4/6 entries of a
+        classified batch, one per distinct key among its redirected headers
+        (verdict > 0) with the value of the last header that wrote the key,
+        ordered by that header -> (records as an (m, 8) int32 tensor in the
+        cfc_proxy4_entry layout — (m, 16) for cfc_proxy6_entry —, the last
+        writers' header indices int64, total records).  Reads `out` as it
+        stands (after ct_apply: the packet-order CT bytes)."""
+        import torch
+        v6 = isinstance(batch, HeaderBatchV6)
+        cap = len(batch) if cap is None else cap
+        dev = out.verdict.device
+        rec = torch.zeros((max(cap, 1), 16 if v6 else 8), dtype=torch.int32, device=dev)
+        idx = torch.zeros(max(cap, 1), dtype=torch.int64, device=dev)
+        cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+        fn = self.L.cfc_proxy_entries_v6 if v6 else self.L.cfc_proxy_entries_v4
+        L.check(fn(self.h, ctypes.byref(hdr_struct(batch)), ctypes.byref(out_struct(out)),
+                   mode, ep_lxc, _ptr(rec), _ptr(idx), cap, _ptr(cnt),
+                   self._stream(stream)), "proxy entries")
+        torch.cuda.synchronize(dev)
+        total = int(cnt.item())
+        m = min(total, cap)
+        return rec[:m], idx[:m], total
+
+    def proxy_apply(self, batch, out: Verdicts, mode=L.MODE_INGRESS, ep_lxc=0,
+                    stream=None):
+        """cfc_proxy_apply_v4/v6: write the batch's proxy-map entries into
+        cilium_proxy4 / cilium_proxy6 (BPF_ANY, in record order) -> the
+        cfc_proxy_stats as a dict {redirects, entries, created, updated,
+        failed}.  Synchronises the stream."""
+        v6 = isinstance(batch, HeaderBatchV6)
+        st = L.ProxyStats()
+        fn = self.L.cfc_proxy_apply_v6 if v6 else self.L.cfc_proxy_apply_v4
+        L.check(fn(self.h, ctypes.byref(hdr_struct(batch)), ctypes.byref(out_struct(out)),
+                   mode, ep_lxc, ctypes.byref(st), self._stream(stream)), "proxy apply")
+        return {k: getattr(st, k) for k, _ in L.ProxyStats._fields_}
+
     def set_clock(self, now):
         """cfc_set_clock: bpf_ktime_get_sec() for the next calls."""
         L.check(self.L.cfc_set_clock(self.h, int(now) & 0xFFFFFFFF), "clock")

@@ -5,7 +5,7 @@ from __future__ import annotations
 
 import struct
 
-from . import cidrmap, ipcache, lbmap, lxcmap, policymap
+from . import cidrmap, ipcache, lbmap, lxcmap, policymap, proxymap
 from .datapath import Datapath
 
 
@@ -60,6 +60,8 @@ def load_tables(dp: Datapath, t, commit=True):
         lbmap.LBMap(dp).load_rows(getattr(t, "lb4", None), getattr(t, "revnat4", None))
     if getattr(t, "lb6", None) is not None or getattr(t, "revnat6", None) is not None:
         lbmap.LBMap6(dp).load_rows(getattr(t, "lb6", None), getattr(t, "revnat6", None))
+    # the proxy maps the datapath writes (Datapath.proxy_apply)
+    dp.proxy = proxymap.ProxyMap(dp)
     if commit:
         dp.commit()
     return pms

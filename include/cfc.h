@@ -74,6 +74,11 @@ int cfc_abi_version(void);
  *                           1..count the backends (pkg/maps/lbmap)
  *   cilium_lb4_reverse_nat  HASH key 2 (rev_nat_index) value 6 (struct
  *                           lb4_reverse_nat {address, port})
+ *   cilium_proxy4           HASH key 10 (struct proxy4_tbl_key) value 16
+ *                           (struct proxy4_tbl_value); a host map with no
+ *                           device table, written by cfc_proxy_apply_v4
+ *   cilium_proxy6           HASH key 22 (struct proxy6_tbl_key) value 28
+ *                           (struct proxy6_tbl_value); cfc_proxy_apply_v6
  * Any other name is a plain map with no datapath role.  Opening an existing
  * path with the same geometry returns a new handle to it (*created = 0);
  * a geometry mismatch returns -EINVAL (pkg/bpf/bpf.go:306 objCheck).
@@ -564,6 +569,97 @@ int cfc_monitor_events_v6(cfc_ctx *ctx, const cfc_hdr_v6 *in, const cfc_out *out
                           int mode, uint16_t ep_lxc, void *records,
                           uint64_t *hdr_index, uint64_t cap, uint64_t *count,
                           void *stream);
+
+/* -------------------------------------------------------------- proxy maps */
+/* What ipv{4,6}_redirect_to_host_port (bpf/lib/lxc.h:96-191) writes into
+ * cilium_proxy4 / cilium_proxy6 for every header the policy sent to the L7
+ * proxy (verdict > 0), so that pkg/proxy can learn where an accepted
+ * connection was going and who sent it (pkg/proxy/socket.go:441), and
+ * pkg/maps/proxymap can expire and clean up the entries.
+ *   key   struct proxy4_tbl_key / proxy6_tbl_key (common.h:478-484, 494-500):
+ *         {saddr = tuple->daddr, dport = the proxy port (the verdict, be16
+ *         raw), sport = tuple->sport, nexthdr, pad 0}
+ *   value struct proxy4_tbl_value / proxy6_tbl_value (:486-492, 502-508):
+ *         {orig_daddr = orig_dip, orig_dport = tuple->dport, pad 0, identity,
+ *         lifetime = the cfc_set_clock time + PROXY_DEFAULT_LIFETIME 720}
+ * Tuple orientation.  ct_lookup4/6 loads the packet's ports as {dport = its
+ * source port, sport = its destination port} and reverses the tuple only
+ * when its first lookup missed (conntrack.h:540-584).  A CT_NEW or
+ * CT_ESTABLISHED header (the CT byte's bits 0-1 of the redirecting stage; no
+ * cfc_out.ct: CT_NEW) therefore has key {the packet's source address and
+ * port} and orig_dport = its destination port; a CT_REPLY or CT_RELATED
+ * header — redirected by the egress stage only (bpf_lxc.c:280, 582 redirect in
+ * every state, the ingress programs in NEW / ESTABLISHED, :851, :985) — has
+ * key {the destination address and port} and orig_dport = its source port.
+ * ICMP has no ports: tuple->sport / dport are what ct_lookup sets for the
+ * type (an echo request: sport = the type, reversed into dport).
+ * Which stage.  An EGRESS header whose CT byte has CFC_CT_DONE in bits 4-7
+ * was redirected by the destination's ipv{4,6}_policy after local delivery,
+ * any other by the sender's egress program.
+ * orig_dip.  Egress stage: tuple.daddr behind the service step
+ * (bpf_lxc.c:181, 501) — cfc_out.pkt_daddr (and the destination port of
+ * pkt_ports) when the batch was service-translated; a flow looped back into
+ * its sender keeps the service address (lb.h:761-770).  With entries in the
+ * family's service map and no pkt_* outputs: -EINVAL.  Destination stage: the
+ * packet as delivered (pkt_* when given).  INGRESS / FULL: the destination
+ * as it arrived (:775, :925).
+ * identity.  EGRESS, both stages: the sender's SECLABEL (cfc_endpoint_config;
+ * the src_label local delivery passes on).  INGRESS / FULL: cfc_out.identity,
+ * all 32 bits.
+ * A header that took a NAT hop gets the entry of its own addresses in its
+ * own family's map.
+ *
+ * Records: key at byte 0, value at byte 16 (IPv4) / 32 (IPv6), padding 0. */
+typedef struct {
+    uint8_t key[10];
+    uint8_t pad0[6];
+    uint8_t value[16];
+} cfc_proxy4_entry;   /* 32 bytes */
+typedef struct {
+    uint8_t key[22];
+    uint8_t pad0[10];
+    uint8_t value[28];
+    uint8_t pad1[4];
+} cfc_proxy6_entry;   /* 64 bytes */
+typedef struct {
+    uint64_t redirects;   /* headers with verdict > 0 */
+    uint64_t entries;     /* records: distinct keys among them */
+    uint64_t created;     /* keys the map did not hold */
+    uint64_t updated;     /* keys it held: value overwritten */
+    uint64_t failed;      /* new keys refused at max_entries: the reference
+                             drops that packet (DROP_PROXYMAP_CREATE_FAILED);
+                             here the verdict is already out */
+} cfc_proxy_stats;
+
+/* The proxy-map entries of one classified batch (in: its headers, out: its
+ * outputs as they stand — after cfc_ct_apply_* the packet-order CT bytes):
+ * one record per distinct key among the redirected headers, carrying the
+ * value of the last header of the batch that wrote the key, ordered by that
+ * header's index.  Arguments as cfc_monitor_events_*: records (16-byte
+ * aligned, else -EINVAL) and hdr_index (may be NULL; the last writer's index)
+ * are device memory, records[0 .. min(total, cap)), *count (device u64) the
+ * total.  Needs out->verdict; out->identity for INGRESS / FULL; out->ct for
+ * EGRESS (-EINVAL).  -ENODEV on a host-only context, -ENOENT when the
+ * family's map (cilium_proxy4 / cilium_proxy6) is not open.
+ * Synchronises `stream` once (the redirect count sizes the workspace); the
+ * records are complete when the work queued on `stream` is. */
+int cfc_proxy_entries_v4(cfc_ctx *ctx, const cfc_hdr_v4 *in, const cfc_out *out,
+                         int mode, uint16_t ep_lxc, cfc_proxy4_entry *records,
+                         uint64_t *hdr_index, uint64_t cap, uint64_t *count,
+                         void *stream);
+int cfc_proxy_entries_v6(cfc_ctx *ctx, const cfc_hdr_v6 *in, const cfc_out *out,
+                         int mode, uint16_t ep_lxc, cfc_proxy6_entry *records,
+                         uint64_t *hdr_index, uint64_t cap, uint64_t *count,
+                         void *stream);
+/* The same records written into the family's map in that order with BPF_ANY
+ * (a full map refuses new keys, -E2BIG in the reference: counted in
+ * st->failed; existing keys still update).  Synchronises `stream`. */
+int cfc_proxy_apply_v4(cfc_ctx *ctx, const cfc_hdr_v4 *in, const cfc_out *out,
+                       int mode, uint16_t ep_lxc, cfc_proxy_stats *st,
+                       void *stream);
+int cfc_proxy_apply_v6(cfc_ctx *ctx, const cfc_hdr_v6 *in, const cfc_out *out,
+                       int mode, uint16_t ep_lxc, cfc_proxy_stats *st,
+                       void *stream);
 
 /* ---------------------------------------------------------------- counters */
 /* The device counter block is a flat u64 array:
