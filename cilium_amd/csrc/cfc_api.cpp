@@ -20,6 +20,7 @@
 #include "../../include/cfc.h"
 #include "classify.hpp"
 #include "selfcut.hpp"
+#include "ctmirror.hpp"
 #include "flatten.hpp"
 #include "maps.hpp"
 
@@ -80,29 +81,30 @@ struct GLb {           // load balancing: services, reverse NAT
     uint64_t bytes = 0;
 };
 struct GCt {           // conntrack
-    DevBuf ct4, ct6, ct_sum;
+    CtTab<Ct4Slot> t4;   // per family (ctmirror.hpp): the table, its host mirror
+    CtTab<Ct6Slot> t6;
+    DevBuf ct_sum;
     // per slot one CtState line (report state, accounting, the device
-    // apply's record): IPv4 slots, then IPv6
+    // apply's record): IPv4 slots, then IPv6 (state_base)
     DevBuf ct_st;
-    DevBuf ct4_lb, ct6_lb;                // per-slot LB state (with a load balancer)
-    DevBuf ct4_ms, ct6_ms;     // device CT apply state (ctapply.hip)
-    // the host mirror: slot -> key as the host maps hold it (to fold the
-    // accounting, patch host-side changes, take the device's records)
-    std::vector<Ct4Slot> ct4_host;
-    std::vector<Ct6Slot> ct6_host;
-    // the device tables' slots (the mirrors' sizes, once any growth's remap
-    // has been applied to them)
-    uint64_t slots4 = 0, slots6 = 0;
-    // a device growth's remap still to apply to a mirror (mirror_sync): per
-    // mirror slot its slot in the current table (NONE: dropped)
-    DevBuf pend4, pend6;
-    std::map<uint64_t, Map *> ct_maps;   // ct_map_key -> map
-    uint32_t ct4_mask = 0, ct4_probe = 0, ct6_mask = 0, ct6_probe = 0;
-    uint32_t n_ct4 = 0, n_ct6 = 0;
-    uint32_t tomb4 = 0, tomb6 = 0;       // deleted slots (CT_TOMBSTONE)
+    CtMaps ct_maps;
     uint32_t n_nat46 = 0;                // IPv4 entries with nat46 at the build
     uint64_t bytes = 0;
 };
+template <bool V6, class G>
+auto &tab(G &g)
+{
+    if constexpr (V6)
+        return g.t6;
+    else
+        return g.t4;
+}
+// where a family's CtState lines (and summaries) start
+template <bool V6>
+uint64_t state_base(const GCt &g)
+{
+    return V6 ? g.t4.slots : 0;
+}
 struct Epoch {
     uint64_t id = 0;
     std::shared_ptr<GIpc> ipc;
@@ -151,23 +153,27 @@ struct cfc_ctx {
     // the device table until ct_sync
     int ct_apply_mode = CFC_CT_APPLY_DEVICE;
     bool ct_dirty = false;
-    uint64_t cta_claims = 0;     // device creates the host mirror lacks (alive)
-    // device-table occupancy for the apply's load check: exact non-free
-    // slots at the last GC (ct_used, while ct_used_valid), plus the inserts
-    // since (cta_ins); otherwise the host's live + tombstone counts
-    uint64_t ct_used = 0, cta_ins = 0;
-    bool ct_used_valid = false;
-    // least CT table slots (a batch outgrew the table: it was rebuilt larger)
-    uint64_t ct_min4 = 0, ct_min6 = 0;
-    // deletes of the device GC (cfc_ct_gc) the host mirror has not taken
-    DevBuf gc_log, gc_tmp, gc_sets, gc_cnt;
-    uint64_t gc_log_used = 0;
-    // the same for the IPv6 table (doGC6), and its exact occupancy after a
-    // GC or a growth (as ct_used for IPv4)
-    DevBuf gc_log6;
-    uint64_t gc_log6_used = 0;
-    uint64_t ct_used6 = 0;
-    bool ct_used6_valid = false;
+    // what the host keeps about each family's device table: [0] IPv4, [1] IPv6
+    struct CtFam {
+        uint64_t claims = 0;     // device creates the host mirror lacks (alive)
+        // device-table occupancy for the apply's load check: exact non-free
+        // slots at the last GC or growth (used, while used_valid), plus the
+        // inserts since (ins); otherwise the host's live + tombstone counts
+        uint64_t used = 0, ins = 0;
+        bool used_valid = false;
+        // least table slots (a batch outgrew the table: it was rebuilt larger)
+        uint64_t min_slots = 0;
+        // deletes of the device GC (cfc_ct_gc) the host mirror has not taken
+        DevBuf gc_log;
+        uint64_t gc_log_used = 0;
+        DevBuf log;              // CtLog / CtLog6
+        uint64_t log_used = 0;   // its entries since the last sync
+        // a device apply or GC delete since the last sync.  Only IPv6's is
+        // set and read (ct_gc collects an IPv6 map without a device table on
+        // the host); IPv4 has no such reader
+        bool dirty = false;
+    } ctf[2];
+    DevBuf gc_tmp, gc_sets, gc_cnt;
     uint32_t cta_seq = 0;
     uint32_t n_apply_dev = 0, n_apply_host = 0;
     // the CT table's version: bumped by every commit that changes tables
@@ -195,8 +201,7 @@ struct cfc_ctx {
     // them — off once a launch's went unused (a lookup-only stream pays
     // nothing), on again when an apply follows its launch
     bool sum_dirty = false, sum_pending = false, sum_want = true;
-    uint64_t log_used = 0;       // CtLog entries since the last sync
-    DevBuf cta_hs, cta_req, cta_req2, cta_cx, cta_cnt, cta_tmp, cta_log, cta_sync, cta_rk;
+    DevBuf cta_hs, cta_req, cta_req2, cta_cx, cta_cnt, cta_tmp, cta_sync, cta_rk;
     DevBuf cta_lbr, cta_reqs;     // a load balancer's service step per header (LbRec4/6)
     DevBuf cta_obm;               // the apply's ordered-slot bitmap
     // packet-order CT results (ctorder.hip): buffers, the deleted-slot
@@ -251,9 +256,6 @@ struct cfc_ctx {
         uint16_t ep = 0;
     };
     std::map<const void *, SegRec> segs;
-    // the IPv6 table's device applies: creates the host lacks, inserts
-    // since the last sync, CtLog6 entries
-    uint64_t cta_claims6 = 0, cta_ins6 = 0, log6_used = 0;
     // a device apply that took no host wait for its own counts (a sparse
     // scan's, route run early): they follow it into pinned host memory and
     // settle() adds them before the next reader of claims / log_used
@@ -261,8 +263,6 @@ struct cfc_ctx {
     uint32_t *pend_cnt = nullptr;   // CTA_NCNT words, pinned
     hipEvent_t pend_ev = nullptr;
     DevBuf cta_cxr;                 // the early route's list
-    DevBuf cta_log6;
-    bool ct6_dirty = false;      // an IPv6 device apply since the last sync
 
     // counters: [n_ctr][2] u64 then metrics
     uint64_t *ctr = nullptr;
@@ -357,52 +357,6 @@ void group_sigs(cfc_ctx *c, uint64_t sig[NGROUPS])
     }
 }
 
-// CT map and key bytes of a device slot (the slot holds the whole tuple)
-Map *ct_slot_key(const Epoch &E, int family, const uint32_t *d, const uint32_t *sa,
-                 uint32_t z, uint32_t w, std::string *key)
-{
-    const uint32_t al = family == 4 ? 4 : 16;
-    char k[38];
-    memcpy(k, d, al);
-    memcpy(k + al, sa, al);
-    memcpy(k + 2 * al, &z, 4);
-    k[2 * al + 4] = (char)(w & 0xFF);
-    k[2 * al + 5] = (char)((w >> 8) & 7);
-    key->assign(k, 2 * al + 6);
-    auto it = E.ct->ct_maps.find(ct_map_key(family, w & ~0x7FFu, (w & 0xFF) != 6));
-    return it == E.ct->ct_maps.end() ? nullptr : it->second;
-}
-
-// struct ct_entry fields the device keeps (CtTimer, CtInfo) into a value:
-// lifetime @32, bits @36 (rx/tx_closing, nat46, seen_non_syn, lb_loopback
-// with a load balancer; others kept), rev_nat_index @38, slave @40 (with a load
-// balancer), tx/rx_flags_seen @42/43, src_sec_id @44, last_tx/rx
-// @48/52
-void ct_value_from_dev(std::string &v, const CtSyncRec &r, bool created)
-{
-    uint16_t bits = 0;
-    if (!created)
-        memcpy(&bits, &v[36], 2);
-    bits = (uint16_t)((bits & ~(1u | 2u | 4u | 16u)) | ((r.flags >> 16) & 3) |
-                      ((r.flags & CTT_NON_SYN) ? 16u : 0u) | ((r.flags & CTT_NAT46) ? 4u : 0u));
-    if (r.pad >> 31) {   // the load balancer's ct_state (ct4_lb / ct6_lb)
-        bits = (uint16_t)((bits & ~8u) | (((r.pad >> 16) & 1) ? 8u : 0u));
-        const uint16_t slave = (uint16_t)(r.pad & 0xFFFF);
-        memcpy(&v[40], &slave, 2);
-    }
-    memcpy(&v[32], &r.lifetime, 4);
-    memcpy(&v[36], &bits, 2);
-    v[42] = (char)((r.flags >> 8) & 0xFF);
-    v[43] = (char)(r.flags & 0xFF);
-    memcpy(&v[48], &r.last_tx, 4);
-    memcpy(&v[52], &r.last_rx, 4);
-    if (created) {
-        const uint16_t rev = (uint16_t)(r.info.y & 0xFFFF);
-        memcpy(&v[38], &rev, 2);
-        memcpy(&v[44], &r.info.sec, 4);
-    }
-}
-
 // a pending apply's counts into the host's bookkeeping (its event waited)
 void settle(cfc_ctx *c)
 {
@@ -411,21 +365,20 @@ void settle(cfc_ctx *c)
     c->pend = false;
     (void)hipEventSynchronize(c->pend_ev);
     const uint32_t *h = c->pend_cnt;
-    uint64_t &claims = c->pend_v6 ? c->cta_claims6 : c->cta_claims;
-    uint64_t &ins = c->pend_v6 ? c->cta_ins6 : c->cta_ins;
-    uint64_t &log_used = c->pend_v6 ? c->log6_used : c->log_used;
-    claims += h[CTA_CLAIMS];
-    ins += h[CTA_CLAIMS];
-    log_used += h[CTA_NLOG];
+    cfc_ctx::CtFam &X = c->ctf[c->pend_v6];
+    X.claims += h[CTA_CLAIMS];
+    X.ins += h[CTA_CLAIMS];
+    X.log_used += h[CTA_NLOG];
 }
 
 // A device growth's remap into the host mirror of one family (ct_grow):
 // the mirror's entries moved to their slots in the current table, plain
-// tombstones dropped with theirs.  *tomb: the mirror's tombstones after.
+// tombstones dropped with theirs; T.tomb: the mirror's tombstones after.
 template <class Slot>
-int remap_mirror(std::vector<Slot> &h, DevBuf &pend, uint64_t slots, uint32_t *tomb,
-                 hipStream_t s)
+int remap_mirror(CtTab<Slot> &T, hipStream_t s)
 {
+    std::vector<Slot> &h = T.host;
+    DevBuf &pend = T.pend;
     if (!pend.p)
         return 0;
     const uint64_t n = h.size();
@@ -433,7 +386,7 @@ int remap_mirror(std::vector<Slot> &h, DevBuf &pend, uint64_t slots, uint32_t *t
     if (n && (hipMemcpyAsync(map.data(), pend.p, 4 * n, hipMemcpyDeviceToHost, s) != hipSuccess ||
               hipStreamSynchronize(s) != hipSuccess))
         return -EIO;
-    std::vector<Slot> nh(slots);
+    std::vector<Slot> nh(T.slots);
     // (tens of millions of scattered copies: spread over the host's cores)
     const unsigned nt = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
     std::vector<uint64_t> tb(nt, 0);
@@ -451,205 +404,104 @@ int remap_mirror(std::vector<Slot> &h, DevBuf &pend, uint64_t slots, uint32_t *t
     uint64_t tt = 0;
     for (uint64_t v : tb)
         tt += v;
-    *tomb = (uint32_t)tt;
+    T.tomb = (uint32_t)tt;
     h.swap(nh);
     pend.reset();
     return 0;
 }
 int mirror_sync(GCt &G, hipStream_t s)
 {
-    if (int rc = remap_mirror(G.ct4_host, G.pend4, G.slots4, &G.tomb4, s))
+    if (int rc = remap_mirror(G.t4, s))
         return rc;
-    return remap_mirror(G.ct6_host, G.pend6, G.slots6, &G.tomb6, s);
+    return remap_mirror(G.t6, s);
 }
 
-// The IPv6 table's part of ct_sync: its dirty slots, then its TCP maps'
-// ICMPv6 entries (CtLog6).
-int ct_sync6(cfc_ctx *c, Epoch &E, hipStream_t s)
+// n records of a device buffer into v (waited for)
+template <class T>
+int download(std::vector<T> &v, const DevBuf &b, uint64_t n, hipStream_t s)
 {
+    v.resize(n);
+    if (n && (hipMemcpyAsync(v.data(), b.p, sizeof(T) * n, hipMemcpyDeviceToHost, s) !=
+                  hipSuccess ||
+              hipStreamSynchronize(s) != hipSuccess))
+        return -EIO;
+    return 0;
+}
+
+// One family's part of ct_sync.  The fetch: its dirty slots (compacted on
+// the device, the deleted ones turned into plain tombstones), the GC's
+// delete log, the TCP maps' ICMP entries (CtLog / CtLog6).  Then their replay
+// into the mirror and the maps (ct_replay, ctmirror.hpp), and the table's
+// exact load.  A family without slots has no dirty records (the launches
+// would find none) but may hold log entries.
+template <bool V6>
+int ct_sync_family(cfc_ctx *c, Epoch &E, hipStream_t s)
+{
+    using F = CtFamily<V6>;
     GCt &G = *E.ct;
-    const uint64_t slots = G.slots6;
+    auto &T = tab<V6>(G);
+    cfc_ctx::CtFam &X = c->ctf[V6];
     uint32_t *cnt = (uint32_t *)c->cta_cnt.p;
-    std::vector<CtSyncRec6> rec;
-    if (slots && G.ct_st.p) {
-        Ct6Slot *ct6 = (Ct6Slot *)G.ct6.p;
-        CtState *st = (CtState *)G.ct_st.p + G.slots4;
-        const uint4 *lb6 = (const uint4 *)G.ct6_lb.p;
+    auto *ct = (typename F::Slot *)T.key.p;
+    std::vector<typename F::SyncRec> rec;
+    if (T.slots && G.ct_st.p) {
+        CtState *st = (CtState *)G.ct_st.p + state_base<V6>(G);
+        const uint4 *lb = (const uint4 *)T.lb.p;
         uint32_t n = 0;
         if (hipMemsetAsync(cnt, 0, 4, s) != hipSuccess ||
-            cta_collect6(ct6, st, lb6, slots, nullptr, 0, cnt, s) ||
+            cta_collect(ct, st, lb, T.slots, nullptr, 0, cnt, s) ||
             hipMemcpyAsync(&n, cnt, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
             hipStreamSynchronize(s) != hipSuccess)
             return -EIO;
         rec.resize(n);
         if (n) {
-            if (c->cta_sync.ensure(sizeof(CtSyncRec6) * n))
+            if (c->cta_sync.ensure(sizeof(rec[0]) * n))
                 return -ENOMEM;
-            CtSyncRec6 *dr = (CtSyncRec6 *)c->cta_sync.p;
+            auto *dr = (typename F::SyncRec *)c->cta_sync.p;
             uint32_t n2 = 0;
             if (hipMemsetAsync(cnt, 0, 4, s) != hipSuccess ||
-                cta_collect6(ct6, st, lb6, slots, dr, n, cnt, s) ||
-                hipMemcpyAsync(rec.data(), dr, sizeof(CtSyncRec6) * n, hipMemcpyDeviceToHost,
-                               s) != hipSuccess ||
+                cta_collect(ct, st, lb, T.slots, dr, n, cnt, s) ||
+                hipMemcpyAsync(rec.data(), dr, sizeof(rec[0]) * n, hipMemcpyDeviceToHost, s) !=
+                    hipSuccess ||
                 hipMemcpyAsync(&n2, cnt, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-                cta_tomb6(ct6, dr, n, s) || hipStreamSynchronize(s) != hipSuccess || n2 != n)
+                cta_tomb(ct, dr, n, s) || hipStreamSynchronize(s) != hipSuccess || n2 != n)
                 return -EIO;
         }
     }
-    std::string key;
-    // the device GC's deletes first (they precede every dirty record of
-    // their slots), as ct_sync does for IPv4
-    if (c->gc_log6_used) {
-        std::vector<CtGcRec6> gl(c->gc_log6_used);
-        if (hipMemcpyAsync(gl.data(), c->gc_log6.p, sizeof(CtGcRec6) * gl.size(),
-                           hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess)
-            return -EIO;
-        for (const CtGcRec6 &r : gl) {
-            uint32_t d[4], sa[4];
-            memcpy(d, &r.d, 16);
-            memcpy(sa, &r.s, 16);
-            if (Map *m = ct_slot_key(E, 6, d, sa, r.z, r.w, &key))
-                m->erase_raw(key);
-            if (r.slot == 0xFFFFFFFFu) {   // (a growth since dropped its tombstone)
-                G.n_ct6--;
-                continue;
-            }
-            Ct6Slot &h = G.ct6_host[r.slot];
-            if (h.z == r.z && h.w == r.w && !memcmp(h.d, d, 16) && !memcmp(h.s, sa, 16)) {
-                G.n_ct6--;
-                G.tomb6++;
-            } else if (h.w == 0) {
-                G.tomb6++;
-            }
-            h = Ct6Slot{};
-            h.w = CT_TOMBSTONE;
-        }
-        c->gc_log6_used = 0;
+    std::vector<typename F::GcRec> gc;
+    std::vector<typename F::Log> log;
+    if (int rc = download(gc, X.gc_log, X.gc_log_used, s))
+        return rc;
+    if (int rc = download(log, X.log, X.log_used, s))
+        return rc;
+    ct_replay<V6>(T, G.ct_maps, gc, rec, log);
+    if (X.gc_log_used)
         for (auto &kv : c->maps)
-            if (kv.second->role == ROLE_CT6)
+            if (kv.second->role == F::role)
                 kv.second->gc_pending = 0;
-    }
-    // deletes first (an entry deleted and created again lives in another
-    // slot), then creates and updates
-    for (int pass = 0; pass < 2; pass++) {
-        for (const CtSyncRec6 &r : rec) {
-            const bool del = (r.w & CT_TOMBSTONE) == CT_TOMBSTONE;
-            if (del != (pass == 0))
-                continue;
-            const uint32_t w = r.w & ~CT_TOMBSTONE;
-            Ct6Slot &h = G.ct6_host[r.slot];
-            const bool prev_live = h.w != 0 && h.w != CT_TOMBSTONE;
-            Map *m = ct_slot_key(E, 6, r.d, r.s, r.z, w, &key);
-            if (del) {
-                if (m)
-                    m->erase_raw(key);
-                if (prev_live) {
-                    G.n_ct6--;
-                    G.tomb6++;
-                } else if (h.w == 0) {
-                    G.tomb6++;
-                }
-                h = Ct6Slot{};
-                h.w = CT_TOMBSTONE;
-            } else if (r.info.y & CTI_CREATED) {
-                if (m) {
-                    CtSyncRec r4{};
-                    r4.info = r.info;
-                    r4.last_rx = r.last_rx;
-                    r4.last_tx = r.last_tx;
-                    r4.flags = r.flags;
-                    r4.lifetime = r.lifetime;
-                    r4.pad = r.pad;
-                    std::string v(m->value_bytes(), '\0');
-                    ct_value_from_dev(v, r4, true);
-                    m->put_raw(key, v);
-                }
-                if (!prev_live) {
-                    G.n_ct6++;
-                    if (h.w == CT_TOMBSTONE)
-                        G.tomb6--;
-                }
-                memcpy(h.d, r.d, 16);
-                memcpy(h.s, r.s, 16);
-                h.z = r.z;
-                h.w = w;
-            } else if (m) {
-                auto it = m->kv.find(key);
-                if (it != m->kv.end() && it->second.val.size() >= 56) {
-                    CtSyncRec r4{};
-                    r4.info = r.info;
-                    r4.last_rx = r.last_rx;
-                    r4.last_tx = r.last_tx;
-                    r4.flags = r.flags;
-                    r4.lifetime = r.lifetime;
-                    r4.pad = r.pad;
-                    ct_value_from_dev(it->second.val, r4, false);
-                }
-            }
-        }
-    }
-    if (c->log6_used) {
-        std::vector<CtLog6> lg(c->log6_used);
-        if (hipMemcpyAsync(lg.data(), c->cta_log6.p, sizeof(CtLog6) * lg.size(),
-                           hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess)
-            return -EIO;
-        std::sort(lg.begin(), lg.end(), [](const CtLog6 &a, const CtLog6 &b) {
-            return a.seq != b.seq ? a.seq < b.seq : a.order < b.order;
-        });
-        for (const CtLog6 &g : lg) {
-            // ct_create6's second write into the TCP map (conntrack.h:648-660)
-            auto it = G.ct_maps.find(ct_map_key(6, g.w & ~0x7FFu, 0));
-            if (it == G.ct_maps.end())
-                continue;
-            char k[38];
-            const uint32_t z = 0;
-            memcpy(k, &g.x, 16);
-            memcpy(k + 16, &g.y, 16);
-            memcpy(k + 32, &z, 4);
-            k[36] = (char)(g.w & 0xFF);
-            k[37] = (char)((g.w >> 8) & 7);
-            std::string v(it->second->value_bytes(), '\0');
-            const uint32_t dir = g.dirlen >> 31;
-            const uint64_t one = 1, len = g.dirlen & (CTLOG_NAT46 - 1);
-            memcpy(&v[dir ? 0 : 16], &one, 8);
-            memcpy(&v[dir ? 8 : 24], &len, 8);
-            const uint32_t life = g.now + 60, last = 5u < g.now ? g.now : 0u;
-            // seen_non_syn ("for ICMP, there is no SYN"), nat46
-            const uint16_t bits = (uint16_t)(16u | ((g.dirlen & CTLOG_NAT46) ? 4u : 0u));
-            const uint16_t rev = (uint16_t)g.rev, slave = (uint16_t)g.slave;
-            memcpy(&v[32], &life, 4);
-            memcpy(&v[36], &bits, 2);
-            memcpy(&v[38], &rev, 2);
-            memcpy(&v[40], &slave, 2);
-            memcpy(&v[44], &g.sec, 4);
-            memcpy(&v[dir ? 52 : 48], &last, 4);
-            it->second->put_raw(std::string(k, 38), v);
-        }
-    }
-    c->log6_used = 0;
-    c->cta_claims6 = 0;
-    c->cta_ins6 = 0;
-    c->ct6_dirty = false;
-    c->ct_used6_valid = false;
-    if (slots) {   // the device's exact load (a GC's trim freed tombstones the mirror holds)
+    X.gc_log_used = 0;
+    X.log_used = 0;
+    X.claims = 0;
+    X.ins = 0;
+    X.dirty = false;
+    X.used_valid = false;
+    if (T.slots) {
+        // the device's exact load: a GC's trim freed tombstones the mirror
+        // still holds as deleted (harmless for probes: a trimmed run ends
+        // its cluster), so the count is taken from the table itself
         uint32_t nonfree = 0;
-        if (hipMemsetAsync(cnt, 0, 4, s) != hipSuccess ||
-            ct_count_nonfree6((const Ct6Slot *)G.ct6.p, slots, cnt, s) ||
+        if (hipMemsetAsync(cnt, 0, 4, s) != hipSuccess || ct_count_nonfree(ct, T.slots, cnt, s) ||
             hipMemcpyAsync(&nonfree, cnt, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
             hipStreamSynchronize(s) != hipSuccess)
             return -EIO;
-        G.tomb6 = nonfree >= G.n_ct6 ? (uint32_t)(nonfree - G.n_ct6) : 0u;
+        T.tomb = nonfree >= T.n ? (uint32_t)(nonfree - T.n) : 0u;
     }
-    E.st.ct6_entries = G.n_ct6;
     return 0;
 }
 
-// The device CT apply's changes into the host mirror of the CT maps: the
-// slots with CtInfo dirty bits (created, updated, deleted) compacted on the
-// device, then the TCP maps' ICMP entries of its creates (CtLog) in batch and
-// header order.  Runs before anything reads or writes a CT map on the host.
+// The device CT apply's changes into the host mirror of the CT maps, IPv4
+// then IPv6 (ct_sync_family).  Runs before anything reads or writes a CT map
+// on the host.
 int ct_sync(cfc_ctx *c, hipStream_t s)
 {
     settle(c);
@@ -662,163 +514,14 @@ int ct_sync(cfc_ctx *c, hipStream_t s)
     // (no ct_gen bump: live entries keep their slots; the deleted ones it
     // turns into tombstones were deleted by an apply, which bumped it)
     Epoch &E = *c->epoch;
-    GCt &G = *E.ct;
-    const uint64_t slots = G.slots4;
-    uint32_t n = 0;
     if (c->cta_cnt.ensure(4 * CTA_NCNT))
         return -ENOMEM;
-    uint32_t *cnt = (uint32_t *)c->cta_cnt.p;
-    Ct4Slot *ct4 = (Ct4Slot *)G.ct4.p;
-    CtState *st = (CtState *)G.ct_st.p;
-    const uint4 *lb4 = (const uint4 *)G.ct4_lb.p;
-    if (hipMemsetAsync(cnt, 0, 4, s) != hipSuccess ||
-        cta_collect(ct4, st, lb4, slots, nullptr, 0, cnt, s) ||
-        hipMemcpyAsync(&n, cnt, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-        return -EIO;
-    std::vector<CtSyncRec> rec(n);
-    if (n) {
-        if (c->cta_sync.ensure(sizeof(CtSyncRec) * n))
-            return -ENOMEM;
-        CtSyncRec *dr = (CtSyncRec *)c->cta_sync.p;
-        uint32_t n2 = 0;
-        if (hipMemsetAsync(cnt, 0, 4, s) != hipSuccess ||
-            cta_collect(ct4, st, lb4, slots, dr, n, cnt, s) ||
-            hipMemcpyAsync(rec.data(), dr, sizeof(CtSyncRec) * n, hipMemcpyDeviceToHost, s) !=
-                hipSuccess ||
-            hipMemcpyAsync(&n2, cnt, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            cta_tomb(ct4, dr, n, s) || hipStreamSynchronize(s) != hipSuccess || n2 != n)
-            return -EIO;
-    }
-    std::string key;
-    // the GC's deletes first (they precede every dirty record of their
-    // slots: a GC clears the slot's dirty bits), then the applies' deletes
-    // (an entry deleted and created again lives in another slot, created
-    // after the delete), then creates and updates
-    if (c->gc_log_used) {
-        std::vector<CtGcRec> gl(c->gc_log_used);
-        if (hipMemcpyAsync(gl.data(), c->gc_log.p, sizeof(CtGcRec) * gl.size(),
-                           hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess)
-            return -EIO;
-        for (const CtGcRec &r : gl) {
-            if (Map *m = ct_slot_key(E, 4, &r.x, &r.y, r.z, r.w, &key))
-                m->erase_raw(key);
-            if (r.slot == 0xFFFFFFFFu) {   // (a growth since dropped its tombstone: ct_grow)
-                G.n_ct4--;
-                continue;
-            }
-            Ct4Slot &h = G.ct4_host[r.slot];
-            if (h.x == r.x && h.y == r.y && h.z == r.z && h.w == r.w) {
-                G.n_ct4--;
-                G.tomb4++;
-            } else if (h.w == 0) {
-                G.tomb4++;
-            }
-            h = Ct4Slot{0, 0, 0, CT_TOMBSTONE};
-        }
-        c->gc_log_used = 0;
-        for (auto &kv : c->maps)
-            if (kv.second->role == ROLE_CT4)
-                kv.second->gc_pending = 0;
-    }
-    for (int pass = 0; pass < 2; pass++) {
-        for (const CtSyncRec &r : rec) {
-            const bool del = (r.w & CT_TOMBSTONE) == CT_TOMBSTONE;
-            if (del != (pass == 0))
-                continue;
-            const uint32_t w = r.w & ~CT_TOMBSTONE;
-            Ct4Slot &h = G.ct4_host[r.slot];
-            const bool prev_live = h.w != 0 && h.w != CT_TOMBSTONE;
-            Map *m = ct_slot_key(E, 4, &r.x, &r.y, r.z, w, &key);
-            if (del) {
-                if (m)
-                    m->erase_raw(key);
-                if (prev_live) {
-                    G.n_ct4--;
-                    G.tomb4++;
-                } else if (h.w == 0) {
-                    G.tomb4++;
-                }
-                h = Ct4Slot{0, 0, 0, CT_TOMBSTONE};
-            } else if (r.info.y & CTI_CREATED) {
-                if (m) {
-                    std::string v(m->value_bytes(), '\0');
-                    ct_value_from_dev(v, r, true);
-                    m->put_raw(key, v);
-                }
-                if (!prev_live) {
-                    G.n_ct4++;
-                    if (h.w == CT_TOMBSTONE)
-                        G.tomb4--;
-                }
-                h = Ct4Slot{r.x, r.y, r.z, w};
-            } else if (m) {
-                auto it = m->kv.find(key);
-                if (it != m->kv.end() && it->second.val.size() >= 56)
-                    ct_value_from_dev(it->second.val, r, false);
-            }
-        }
-    }
-    if (c->log_used) {
-        std::vector<CtLog> lg(c->log_used);
-        if (hipMemcpyAsync(lg.data(), c->cta_log.p, sizeof(CtLog) * lg.size(),
-                           hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess)
-            return -EIO;
-        std::sort(lg.begin(), lg.end(), [](const CtLog &a, const CtLog &b) {
-            return a.seq != b.seq ? a.seq < b.seq : a.order < b.order;
-        });
-        for (const CtLog &g : lg) {
-            // ct_create4's second write into the TCP map (conntrack.h:741-760)
-            auto it = G.ct_maps.find(ct_map_key(4, g.w & ~0x7FFu, 0));
-            if (it == G.ct_maps.end())
-                continue;
-            char k[14];
-            const uint32_t z = 0;
-            memcpy(k, &g.x, 4);
-            memcpy(k + 4, &g.y, 4);
-            memcpy(k + 8, &z, 4);
-            k[12] = (char)(g.w & 0xFF);
-            k[13] = (char)((g.w >> 8) & 7);
-            std::string v(it->second->value_bytes(), '\0');
-            const uint32_t dir = g.dirlen >> 31;
-            const uint64_t one = 1, len = g.dirlen & (CTLOG_NAT46 - 1);
-            memcpy(&v[dir ? 0 : 16], &one, 8);
-            memcpy(&v[dir ? 8 : 24], &len, 8);
-            const uint32_t life = g.now + 60, last = 5u < g.now ? g.now : 0u;
-            // seen_non_syn ("for ICMP, there is no SYN"), and a load
-            // balancer's ct_state
-            const uint16_t bits = (uint16_t)(16u | (((g.lbw >> 16) & 1) ? 8u : 0u) |
-                                             ((g.dirlen & CTLOG_NAT46) ? 4u : 0u));
-            const uint16_t rev = (uint16_t)(g.lbw & 0xFFFF), slave = (uint16_t)g.slave;
-            memcpy(&v[32], &life, 4);
-            memcpy(&v[36], &bits, 2);
-            memcpy(&v[38], &rev, 2);
-            memcpy(&v[40], &slave, 2);
-            memcpy(&v[44], &g.sec, 4);
-            memcpy(&v[dir ? 52 : 48], &last, 4);
-            it->second->put_raw(std::string(k, 14), v);
-        }
-    }
-    c->log_used = 0;
-    c->cta_claims = 0;
-    c->cta_ins = 0;
-    c->ct_used_valid = false;
-    {   // the device's exact load: a GC's trim freed tombstones the mirror
-        // still holds as deleted (harmless for probes: a trimmed run ends
-        // its cluster), so the count is taken from the table itself
-        uint32_t nonfree = 0;
-        if (hipMemsetAsync(cnt, 0, 4, s) != hipSuccess ||
-            ct_count_nonfree4(ct4, slots, cnt, s) ||
-            hipMemcpyAsync(&nonfree, cnt, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess)
-            return -EIO;
-        G.tomb4 = nonfree >= G.n_ct4 ? (uint32_t)(nonfree - G.n_ct4) : 0u;
-    }
-    E.st.ct4_entries = G.n_ct4;
-    if (int rc = ct_sync6(c, E, s))
+    if (int rc = ct_sync_family<false>(c, E, s))
         return rc;
+    E.st.ct4_entries = E.ct->t4.n;
+    if (int rc = ct_sync_family<true>(c, E, s))
+        return rc;
+    E.st.ct6_entries = E.ct->t6.n;
     c->ct_dirty = false;
     return 0;
 }
@@ -830,12 +533,13 @@ int fold_ct(cfc_ctx *c, hipStream_t s)
     if (int rc = ct_sync(c, s))
         return rc;
     Epoch &E = *c->epoch;
-    const size_t n4 = E.ct->slots4, n = n4 + E.ct->slots6;
+    const GCt &G = *E.ct;
+    const size_t n4 = G.t4.slots, n = n4 + G.t6.slots;
     if (!n)
         return 0;
     std::vector<uint64_t> h(4 * n);
     DevBuf tmp;   // (the lines' counts, dense)
-    if (tmp.ensure(32 * n) || ct_acct_take((CtState *)E.ct->ct_st.p, (uint64_t *)tmp.p, n, s) ||
+    if (tmp.ensure(32 * n) || ct_acct_take((CtState *)G.ct_st.p, (uint64_t *)tmp.p, n, s) ||
         hipMemcpyAsync(h.data(), tmp.p, 32 * n, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
         return -EIO;
@@ -844,14 +548,8 @@ int fold_ct(cfc_ctx *c, hipStream_t s)
         const uint64_t *a = &h[4 * i];
         if (!(a[0] | a[1] | a[2] | a[3]))
             continue;
-        Map *m;
-        if (i < n4) {
-            const Ct4Slot &e = E.ct->ct4_host[i];
-            m = ct_slot_key(E, 4, &e.x, &e.y, e.z, e.w, &key);
-        } else {
-            const Ct6Slot &e = E.ct->ct6_host[i - n4];
-            m = ct_slot_key(E, 6, e.d, e.s, e.z, e.w, &key);
-        }
+        Map *m = i < n4 ? ct_slot_key(G.ct_maps, 4, CtFamily<false>::key(G.t4.host[i]), &key)
+                        : ct_slot_key(G.ct_maps, 6, CtFamily<true>::key(G.t6.host[i - n4]), &key);
         if (!m)
             continue;
         auto it = m->kv.find(key);
@@ -1137,9 +835,8 @@ std::shared_ptr<GCt> build_ctg(HostImage &img, const std::vector<Map *> &ms, hip
                                int *rc)
 {
     auto g = std::make_shared<GCt>();
-    if ((*rc = upload_vec(g->ct4, img.ct4, s)) || (*rc = upload_vec(g->ct6, img.ct6, s)) ||
-        (*rc = upload_vec(g->ct4_lb, img.ct4_lb, s)) ||
-        (*rc = upload_vec(g->ct6_lb, img.ct6_lb, s)))
+    if ((*rc = upload_vec(g->t4.key, img.ct4, s)) || (*rc = upload_vec(g->t6.key, img.ct6, s)) ||
+        (*rc = upload_vec(g->t4.lb, img.ct4_lb, s)) || (*rc = upload_vec(g->t6.lb, img.ct6_lb, s)))
         return nullptr;
     const size_t nslots = img.ct4.size() + img.ct6.size();
     if (nslots && (*rc = g->ct_sum.zeros(4 * nslots, s)))
@@ -1167,9 +864,9 @@ std::shared_ptr<GCt> build_ctg(HostImage &img, const std::vector<Map *> &ms, hip
             }
         }
     }
-    if (n4 && (*rc = g->ct4_ms.zeros(12 * n4, s)))   // (ms, then lh)
+    if (n4 && (*rc = g->t4.ms.zeros(12 * n4, s)))   // (ms, then lh)
         return nullptr;
-    if (n6 && (*rc = g->ct6_ms.zeros(12 * n6, s)))
+    if (n6 && (*rc = g->t6.ms.zeros(12 * n6, s)))
         return nullptr;
     for (Map *m : ms)
         if (m->role == ROLE_CT4 || m->role == ROLE_CT6)
@@ -1177,19 +874,19 @@ std::shared_ptr<GCt> build_ctg(HostImage &img, const std::vector<Map *> &ms, hip
                                   ct_owner_word((uint32_t)std::max(m->policy_lxc, 0),
                                                 m->policy_lxc >= 0),
                                   m->ct_any)] = m;
-    g->ct4_mask = img.ct4_mask;
-    g->ct4_probe = img.ct4_probe;
-    g->ct6_mask = img.ct6_mask;
-    g->ct6_probe = img.ct6_probe;
-    g->n_ct4 = img.n_ct4;
-    g->n_ct6 = img.n_ct6;
+    g->t4.mask = img.ct4_mask;
+    g->t4.probe = img.ct4_probe;
+    g->t6.mask = img.ct6_mask;
+    g->t6.probe = img.ct6_probe;
+    g->t4.n = img.n_ct4;
+    g->t6.n = img.n_ct6;
     g->n_nat46 = img.n_nat46;
     g->bytes = sizeof(Ct4Slot) * img.ct4.size() + sizeof(Ct6Slot) * img.ct6.size() +
                (sizeof(CtState) + 4) * nslots + 8ull * (n4 + n6) + 16ull * img.ct4_lb.size();
-    g->slots4 = img.ct4.size();
-    g->slots6 = img.ct6.size();
-    g->ct4_host = std::move(img.ct4);
-    g->ct6_host = std::move(img.ct6);
+    g->t4.slots = img.ct4.size();
+    g->t6.slots = img.ct6.size();
+    g->t4.host = std::move(img.ct4);
+    g->t6.host = std::move(img.ct6);
     return g;
 }
 
@@ -1233,24 +930,24 @@ void assemble(Epoch &E)
     T.pol_bloom_words = D.pol_bloom_words;
     T.n_ctr = (uint32_t)D.ctr_owner.size();
     // (a table a device apply may fill counts even while empty)
-    T.ct4 = (C.n_ct4 || C.slots4) ? (const Ct4Slot *)C.ct4.p : nullptr;
-    T.ct6 = (C.n_ct6 || C.slots6) ? (const Ct6Slot *)C.ct6.p : nullptr;
+    T.ct4 = (C.t4.n || C.t4.slots) ? (const Ct4Slot *)C.t4.key.p : nullptr;
+    T.ct6 = (C.t6.n || C.t6.slots) ? (const Ct6Slot *)C.t6.key.p : nullptr;
     T.ct_st = (CtState *)C.ct_st.p;
     T.ct_sum = (uint32_t *)C.ct_sum.p;
-    T.ct4_mask = C.ct4_mask;
+    T.ct4_mask = C.t4.mask;
     // the device CT apply inserts in place: lookups walk to a free slot
-    T.ct4_probe = C.ct4_mask;
-    T.ct6_mask = C.ct6_mask;
-    T.ct6_probe = C.ct6_mask;
-    T.ct6_acct_base = (uint32_t)C.slots4;
+    T.ct4_probe = C.t4.mask;
+    T.ct6_mask = C.t6.mask;
+    T.ct6_probe = C.t6.mask;
+    T.ct6_acct_base = (uint32_t)state_base<true>(C);
     T.lb4 = B.n_lb4 ? (const uint4 *)B.lb4.p : nullptr;
     T.lb4_mask = B.lb4_mask;
     T.rnat4 = (const uint2 *)B.rnat4.p;
-    T.ct4_lb = T.ct4 ? (const uint4 *)C.ct4_lb.p : nullptr;
+    T.ct4_lb = T.ct4 ? (const uint4 *)C.t4.lb.p : nullptr;
     T.lb6 = B.n_lb6 ? (const uint4 *)B.lb6.p : nullptr;
     T.lb6_mask = B.lb6_mask;
     T.rnat6 = (const uint4 *)B.rnat6.p;
-    T.ct6_lb = T.ct6 ? (const uint4 *)C.ct6_lb.p : nullptr;
+    T.ct6_lb = T.ct6 ? (const uint4 *)C.t6.lb.p : nullptr;
     cfc_stats &st = E.st;
     st = cfc_stats{};
     st.epoch = E.id;
@@ -1270,8 +967,8 @@ void assemble(Epoch &E)
     st.endpoints_v6 = D.n_eps6;
     st.prefilter_v6_fix = P.n_fix6;
     st.prefilter_v6_dyn = P.n_dyn6;
-    st.ct4_entries = C.n_ct4;
-    st.ct6_entries = C.n_ct6;
+    st.ct4_entries = C.t4.n;
+    st.ct6_entries = C.t6.n;
 }
 
 // Build the next epoch: re-flatten and upload the groups whose maps changed,
@@ -1364,8 +1061,8 @@ unsigned patch_touched(cfc_ctx *c, unsigned groups, hipStream_t s)
             groups |= GROUP_CT;
         } else {
             const GCt &G = *E.ct;
-            E.st.ct4_entries = G.n_ct4;
-            E.st.ct6_entries = G.n_ct6;
+            E.st.ct4_entries = G.t4.n;
+            E.st.ct6_entries = G.t6.n;
         }
     }
     return groups;
@@ -1394,8 +1091,9 @@ bool patch_ct(cfc_ctx *c, hipStream_t s)
             any[f]++;
             ins[f] += (t.second & TOUCH_INSERT) ? 1 : 0;
             // an entry with LB state into a table without the LB state
-            // array: rebuilt with it
-            if (!f && !G.ct4_lb.p) {
+            // array: rebuilt with it (IPv4 only: an IPv6 table without the
+            // array drops the word, below)
+            if (!f && !G.t4.lb.p) {
                 auto it = m->kv.find(t.first);
                 if (it != m->kv.end()) {
                     const uint4 l = ct_lb_of(it->second.val);
@@ -1405,11 +1103,11 @@ bool patch_ct(cfc_ctx *c, hipStream_t s)
             }
         }
     }
-    const uint64_t size[2] = {G.slots4, G.slots6};
-    const uint64_t used[2] = {(uint64_t)G.n_ct4 + G.tomb4, (uint64_t)G.n_ct6 + G.tomb6};
-    for (int f = 0; f < 2; f++)
-        if (any[f] && (!size[f] || 4 * (used[f] + ins[f]) > 3 * size[f]))
-            return false;
+    auto full = [&](const auto &T, int f) {
+        return any[f] && (!T.slots || 4 * (T.used() + ins[f]) > 3 * T.slots);
+    };
+    if (full(G.t4, 0) || full(G.t6, 1))
+        return false;
     std::unordered_map<uint64_t, size_t> at_addr;
     std::vector<Patch16> &rec = c->patch_host;
     rec.clear();
@@ -1429,104 +1127,88 @@ bool patch_ct(cfc_ctx *c, hipStream_t s)
         put(a, zero);
         put(a + 16, zero);
     };
-    for (auto &kv : c->maps) {
-        Map *m = kv.second.get();
-        if (!m->ct() || m->touched.empty())
-            continue;
-        const bool v6 = m->role == ROLE_CT6;
-        for (auto &t : m->touched) {
-            Ct4Slot k4;
-            Ct6Slot k6;
-            if (!ct_slot_of(m, t.first, &k4, &k6))
-                continue;   // no lookup reaches it: not in the device table
-            auto it = m->kv.find(t.first);
-            const bool present = it != m->kv.end();
-            // the key's slot, else the first free or deleted one
-            const uint32_t mask = (uint32_t)size[v6] - 1;
-            int64_t at = -1, slot = -1;
-            uint32_t p = 0, pfree = 0;
-            uint32_t i = v6 ? ct_home6(k6.d, k6.s, k6.z, k6.w) & mask
-                            : ct_home4(k4.x, k4.y, k4.z, k4.w) & mask;
-            for (;; i = (i + 1) & mask, p++) {
-                const uint32_t w = v6 ? G.ct6_host[i].w : G.ct4_host[i].w;
-                if (w == 0 || w == CT_TOMBSTONE) {
-                    if (slot < 0) {
-                        slot = i;
-                        pfree = p;
-                    }
-                    if (w == 0)
-                        break;
-                    continue;
+    // one journal entry t of map m, of family V6 (fam: std::bool_constant)
+    auto one = [&](auto fam, Map *m, const std::pair<const std::string, int> &t) {
+        constexpr bool V6 = decltype(fam)::value;
+        using F = CtFamily<V6>;
+        using Slot = typename F::Slot;
+        auto &T = tab<V6>(G);
+        Slot k;
+        bool reached;
+        if constexpr (V6)
+            reached = ct_slot_of(m, t.first, nullptr, &k);
+        else
+            reached = ct_slot_of(m, t.first, &k, nullptr);
+        if (!reached)
+            return;   // no lookup reaches it: not in the device table
+        auto it = m->kv.find(t.first);
+        const bool present = it != m->kv.end();
+        // the key's slot, else the first free or deleted one
+        const uint32_t mask = (uint32_t)T.slots - 1;
+        int64_t at = -1, slot = -1;
+        uint32_t p = 0, pfree = 0;
+        for (uint32_t i = F::home(F::key(k)) & mask;; i = (i + 1) & mask, p++) {
+            const uint32_t w = T.host[i].w;
+            if (w == 0 || w == CT_TOMBSTONE) {
+                if (slot < 0) {
+                    slot = i;
+                    pfree = p;
                 }
-                const bool eq = v6 ? (G.ct6_host[i].z == k6.z && w == k6.w &&
-                                      !memcmp(G.ct6_host[i].d, k6.d, 16) &&
-                                      !memcmp(G.ct6_host[i].s, k6.s, 16))
-                                   : (G.ct4_host[i].x == k4.x && G.ct4_host[i].y == k4.y &&
-                                      G.ct4_host[i].z == k4.z && w == k4.w);
-                if (eq) {
-                    at = i;
+                if (w == 0)
                     break;
-                }
+                continue;
             }
-            const uint64_t acct = v6 ? size[0] + (uint64_t)(at >= 0 ? at : slot)
-                                     : (uint64_t)(at >= 0 ? at : slot);
-            CtState *tm = (CtState *)G.ct_st.p + (v6 ? size[0] : 0);
-            if (present) {
-                const CtTimer v = ct_timer_of(it->second.val);
-                c->nat46_seen |= !v6 && (v.flags & CTT_NAT46);
-                if (at < 0) {   // insert
-                    at = slot;
-                    if (v6) {
-                        const bool tomb = G.ct6_host[at].w == CT_TOMBSTONE;
-                        G.tomb6 -= tomb;
-                        G.n_ct6++;
-                        G.ct6_host[at] = k6;
-                        G.ct6_probe = std::max(G.ct6_probe, pfree);
-                        const uint32_t *w = (const uint32_t *)&k6;
-                        char *d = (char *)G.ct6.p + sizeof(Ct6Slot) * at;
-                        put(d, w);
-                        put(d + 16, w + 4);
-                        put(d + 32, w + 8);
-                    } else {
-                        const bool tomb = G.ct4_host[at].w == CT_TOMBSTONE;
-                        G.tomb4 -= tomb;
-                        G.n_ct4++;
-                        G.ct4_host[at] = k4;
-                        G.ct4_probe = std::max(G.ct4_probe, pfree);
-                        put((char *)G.ct4.p + sizeof(Ct4Slot) * at, &k4);
-                    }
-                    zero_acct(acct);
-                } else if (t.second & (TOUCH_INSERT | TOUCH_ERASE)) {
-                    zero_acct(acct);   // deleted and created again
-                }
-                put(&tm[at].tm, &v);
-                const uint4 l = ct_lb_of(it->second.val);
-                if (!v6 && G.ct4_lb.p)
-                    put((uint4 *)G.ct4_lb.p + at, &l);
-                if (v6 && G.ct6_lb.p) {
-                    const uint4 l6 = make_uint4(l.x & 0xFFFF, l.y, 0, 0);
-                    put((uint4 *)G.ct6_lb.p + at, &l6);
-                }
-            } else if (at >= 0) {       // delete
-                if (v6) {
-                    Ct6Slot d{};
-                    d.w = CT_TOMBSTONE;
-                    G.ct6_host[at] = d;
-                    G.n_ct6--;
-                    G.tomb6++;
-                    const uint32_t *w = (const uint32_t *)&d;
-                    char *dst = (char *)G.ct6.p + sizeof(Ct6Slot) * at;
-                    put(dst + 32, w + 8);   // z, w: probes compare these first
-                } else {
-                    const Ct4Slot d{0, 0, 0, CT_TOMBSTONE};
-                    G.ct4_host[at] = d;
-                    G.n_ct4--;
-                    G.tomb4++;
-                    put((char *)G.ct4.p + sizeof(Ct4Slot) * at, &d);
-                }
-                zero_acct(acct);
+            if (ct_key_eq<V6>(F::key(T.host[i]), F::key(k))) {
+                at = i;
+                break;
             }
         }
+        const uint64_t base = state_base<V6>(G), acct = base + (uint64_t)(at >= 0 ? at : slot);
+        CtState *tm = (CtState *)G.ct_st.p + base;
+        if (present) {
+            const CtTimer v = ct_timer_of(it->second.val);
+            c->nat46_seen |= !V6 && (v.flags & CTT_NAT46);   // (only IPv4 entries carry it)
+            if (at < 0) {   // insert
+                at = slot;
+                T.tomb -= T.host[at].w == CT_TOMBSTONE;
+                T.n++;
+                T.host[at] = k;
+                T.probe = std::max(T.probe, pfree);
+                for (size_t o = 0; o < sizeof(Slot); o += 16)
+                    put((char *)T.key.p + sizeof(Slot) * at + o, (const char *)&k + o);
+                zero_acct(acct);
+            } else if (t.second & (TOUCH_INSERT | TOUCH_ERASE)) {
+                zero_acct(acct);   // deleted and created again
+            }
+            put(&tm[at].tm, &v);
+            if (T.lb.p) {
+                // (an IPv6 slot's LB word: rev_nat_index without the loopback
+                // bit, slave; no addresses)
+                const uint4 l = ct_lb_of(it->second.val),
+                            lw = V6 ? make_uint4(l.x & 0xFFFF, l.y, 0, 0) : l;
+                put((uint4 *)T.lb.p + at, &lw);
+            }
+        } else if (at >= 0) {       // delete
+            const Slot d = F::tombstone();
+            T.host[at] = d;
+            T.n--;
+            T.tomb++;
+            // (the slot's last 16 bytes — all of an IPv4 slot — hold z, w:
+            // probes compare these first)
+            const size_t o = sizeof(Slot) - 16;
+            put((char *)T.key.p + sizeof(Slot) * at + o, (const char *)&d + o);
+            zero_acct(acct);
+        }
+    };
+    for (auto &kv : c->maps) {
+        Map *m = kv.second.get();
+        if (!m->ct())
+            continue;
+        for (auto &t : m->touched)
+            if (m->role == ROLE_CT6)
+                one(std::true_type{}, m, t);
+            else
+                one(std::false_type{}, m, t);
     }
     if (rec.empty())
         return true;
@@ -1585,8 +1267,8 @@ int commit_locked(cfc_ctx *c, hipStream_t s)
     for (auto &kv : c->maps)
         ms.push_back(kv.second.get());
     HostImage img;
-    img.ct_min4 = c->ct_min4;
-    img.ct_min6 = c->ct_min6;
+    img.ct_min4 = c->ctf[0].min_slots;
+    img.ct_min6 = c->ctf[1].min_slots;
     build_image(ms, c->opts, &img, groups);
 
     auto E = std::make_shared<Epoch>();
@@ -3102,8 +2784,9 @@ int cfc_get_stats(cfc_ctx *c, cfc_stats *st)
     st->ct_self_segments = c->n_self_segs;
     st->ct_apply_sparse = c->n_apply_sparse;
     st->ct_grown = (uint32_t)c->n_ct_grow;
-    st->ct_slots = (c->epoch && c->epoch->ct) ? (uint32_t)(c->epoch->ct->slots4 + c->epoch->ct->slots6)
-                            : 0u;
+    st->ct_slots = 0;
+    if (c->epoch && c->epoch->ct)
+        st->ct_slots = (uint32_t)(c->epoch->ct->t4.slots + c->epoch->ct->t6.slots);
     return 0;
 }
 
@@ -3530,48 +3213,38 @@ LbState lb4_step(const LbHost &L, Map *m, uint32_t sa, uint32_t da, uint32_t &pt
 // removes or replaces an entry drops the counts the batch's lookups made on
 // it (in the reference they land on the entry before it goes), so its
 // accounting slot is zeroed before the fold.
-int64_t ct_dev_slot(const Epoch &E, const Map *m, const std::string &k)
+template <bool V6>
+int64_t ct_dev_slot_of(const GCt &G, const Map *m, const std::string &k)
 {
-    const bool v6 = m->role == ROLE_CT6;
-    const size_t al = v6 ? 16 : 4;
+    using F = CtFamily<V6>;
+    constexpr size_t al = F::al;
+    const auto &T = tab<V6>(G);
     const uint32_t owner = ct_owner_word((uint32_t)std::max(m->policy_lxc, 0),
                                          m->policy_lxc >= 0);
-    uint32_t z;
-    memcpy(&z, k.data() + 2 * al, 4);
     const uint8_t nh = (uint8_t)k[2 * al + 4];
     // entries no lookup reaches are not in the device table (build_ct); the
     // same tuple in the other map kind is a different entry
-    if (m->ct_any ? (nh != 17 && nh != (v6 ? 58 : 1)) : nh != 6)
+    if (m->ct_any ? (nh != 17 && nh != (V6 ? 58 : 1)) : nh != 6)
         return -1;
-    const uint32_t w = ct_word(nh, (uint8_t)k[2 * al + 5], owner);
-    if (!v6) {
-        if (!E.ct->slots4)
-            return -1;
-        uint32_t x, y;
-        memcpy(&x, k.data(), 4);
-        memcpy(&y, k.data() + 4, 4);
-        const uint32_t mask = (uint32_t)E.ct->slots4 - 1;
-        for (uint32_t i = ct_home4(x, y, z, w) & mask;; i = (i + 1) & mask) {
-            const Ct4Slot &e = E.ct->ct4_host[i];
-            if (!e.w)
-                return -1;
-            if (e.x == x && e.y == y && e.z == z && e.w == w)
-                return i;
-        }
-    }
-    if (!E.ct->slots6)
+    if (!T.slots)
         return -1;
     uint32_t d[4], sa[4];
-    memcpy(d, k.data(), 16);
-    memcpy(sa, k.data() + 16, 16);
-    const uint32_t mask = (uint32_t)E.ct->slots6 - 1;
-    for (uint32_t i = ct_home6(d, sa, z, w) & mask;; i = (i + 1) & mask) {
-        const Ct6Slot &e = E.ct->ct6_host[i];
-        if (!e.w)
+    CtKey key{d, sa, 0, ct_word(nh, (uint8_t)k[2 * al + 5], owner)};
+    memcpy(d, k.data(), al);
+    memcpy(sa, k.data() + al, al);
+    memcpy(&key.z, k.data() + 2 * al, 4);
+    const uint32_t mask = (uint32_t)T.slots - 1;
+    for (uint32_t i = F::home(key) & mask;; i = (i + 1) & mask) {
+        if (!T.host[i].w)
             return -1;
-        if (e.z == z && e.w == w && !memcmp(e.d, d, 16) && !memcmp(e.s, sa, 16))
-            return (int64_t)E.ct->slots4 + i;
+        if (ct_key_eq<V6>(F::key(T.host[i]), key))
+            return (int64_t)state_base<V6>(G) + i;
     }
+}
+int64_t ct_dev_slot(const Epoch &E, const Map *m, const std::string &k)
+{
+    return m->role == ROLE_CT6 ? ct_dev_slot_of<true>(*E.ct, m, k)
+                               : ct_dev_slot_of<false>(*E.ct, m, k);
 }
 
 void ct_drop_counts(cfc_ctx *c, const Map *m, const std::string &k, hipStream_t s)
@@ -3582,9 +3255,6 @@ void ct_drop_counts(cfc_ctx *c, const Map *m, const std::string &k, hipStream_t 
     if (slot >= 0)
         (void)hipMemsetAsync(((CtState *)c->epoch->ct->ct_st.p + slot)->acct, 0, 32, s);
 }
-
-int ct_gc_dev(cfc_ctx *c, const std::vector<Map *> &sel, const cfc_ct_gc_filter &f,
-              cfc_ct_gc_stats &st, hipStream_t s, const uint32_t *protect);
 
 // A batch whose creates would take CT maps past max_entries (want[j]: the
 // entries map j would hold): the reference's LRU hash evicts its least
@@ -3600,7 +3270,8 @@ int ct_gc_dev(cfc_ctx *c, const std::vector<Map *> &sel, const cfc_ct_gc_filter 
 // checked before any is touched: 0 done, 1 a map has too few candidates
 // (nothing deleted: the host path), 2 deleted but the table could not be
 // patched (the host path; the next commit rebuilds), < 0 error.
-int ct_evict_maps(cfc_ctx *c, bool v6, const std::vector<Map *> &fmaps,
+template <bool V6>
+int ct_evict_maps(cfc_ctx *c, const std::vector<Map *> &fmaps,
                   const std::vector<uint64_t> &want, const uint32_t *hs, uint64_t nk,
                   hipStream_t s)
 {
@@ -3608,8 +3279,8 @@ int ct_evict_maps(cfc_ctx *c, bool v6, const std::vector<Map *> &fmaps,
     GCt &G = *E.ct;
     if (int rc = mirror_sync(G, s))
         return rc;
-    const uint64_t slots = v6 ? G.slots6 : G.slots4;
-    const uint64_t base6 = v6 ? G.slots4 : 0;   // (ct_dev_slot's IPv6 offset)
+    const uint64_t slots = tab<V6>(G).slots;
+    const uint64_t base = state_base<V6>(G);   // (ct_dev_slot's offset)
     const size_t words = (slots + 31) / 32;
     std::vector<uint32_t> bm(words);
     if (c->evict_bm.ensure(4 * words) ||
@@ -3630,13 +3301,13 @@ int ct_evict_maps(cfc_ctx *c, bool v6, const std::vector<Map *> &fmaps,
         if (want[j] <= m->max_entries)
             continue;
         const uint64_t excess = want[j] - m->max_entries;
-        const size_t al = v6 ? 16 : 4;
+        const size_t al = CtFamily<V6>::al;
         std::vector<Cand> cand;
         cand.reserve(m->kv.size());
         for (It it = m->kv.begin(); it != m->kv.end(); ++it) {
             const int64_t ds = ct_dev_slot(E, m, it->first);
             if (ds >= 0) {
-                const uint64_t sl = (uint64_t)ds - base6;
+                const uint64_t sl = (uint64_t)ds - base;
                 if (sl < slots && ((bm[sl >> 5] >> (sl & 31)) & 1u))
                     continue;   // hit by this batch
             }
@@ -3687,13 +3358,13 @@ int ct_evict_maps(cfc_ctx *c, bool v6, const std::vector<Map *> &fmaps,
     for (auto &kv : c->maps)
         if (kv.second->ct())
             kv.second->touched.clear();
-    E.st.ct4_entries = G.n_ct4;
-    E.st.ct6_entries = G.n_ct6;
+    E.st.ct4_entries = G.t4.n;
+    E.st.ct6_entries = G.t6.n;
     c->ct_gen++;
     return hipStreamSynchronize(s) == hipSuccess ? 0 : -EIO;
 }
 
-// Device-side growth of family v6's CT table to `want` slots (a power of
+// Device-side growth of family V6's CT table to `want` slots (a power of
 // two): the rehash kernel (ctapply.hip k_ct_rehash) moves every key-holding
 // slot, its CtState line and LB word into new buffers; the other family's
 // lines are copied as they are (the IPv6 lines start after the IPv4 ones);
@@ -3702,51 +3373,51 @@ int ct_evict_maps(cfc_ctx *c, bool v6, const std::vector<Map *> &fmaps,
 // reader), and the pending GC log's slots are remapped on the device.  The
 // replaced buffers are retired like an epoch (launches on other streams may
 // still read them).  0 grown, 1 not possible (the host path), < 0 error.
-int ct_grow(cfc_ctx *c, bool v6, uint64_t want, hipStream_t s)
+template <bool V6>
+int ct_grow(cfc_ctx *c, uint64_t want, hipStream_t s)
 {
+    using F = CtFamily<V6>;
     Epoch &E = *c->epoch;
     GCt &G = *E.ct;
-    const uint64_t n4 = G.slots4, n6 = G.slots6, o = v6 ? n6 : n4;
+    auto &T = tab<V6>(G);
+    cfc_ctx::CtFam &X = c->ctf[V6];
+    const uint64_t o = T.slots, other = tab<!V6>(G).slots;
     if (!o || want <= o || want > (1ull << 30) || (want & (want - 1)))
         return 1;
-    const uint64_t m4 = v6 ? n4 : want, m6 = v6 ? want : n6;
-    const size_t ksz = v6 ? sizeof(Ct6Slot) : sizeof(Ct4Slot);
-    DevBuf &key = v6 ? G.ct6 : G.ct4, &lb = v6 ? G.ct6_lb : G.ct4_lb, &ms = v6 ? G.ct6_ms : G.ct4_ms;
+    // the lines of both families, IPv4's first: this family's start where
+    // they did, the other's move behind a grown IPv4 table
+    const uint64_t own = state_base<V6>(G), oth_old = V6 ? 0 : o, oth_new = V6 ? 0 : want,
+                   lines = want + other;
+    const size_t ksz = sizeof(typename F::Slot);
+    DevBuf &lb = T.lb;
     auto nk = std::make_unique<DevBuf>(), nst = std::make_unique<DevBuf>(),
          nsum = std::make_unique<DevBuf>(), nms = std::make_unique<DevBuf>(),
          nlb = std::make_unique<DevBuf>();
     DevBuf map;
     // (every new line zero: the rehash writes only the moved slots', and a
     // free slot's record must read as no entry, no dirty bits)
-    if (nk->zeros(ksz * want, s) || nst->zeros(sizeof(CtState) * (m4 + m6), s) ||
-        nsum->zeros(4 * (m4 + m6), s) || nms->zeros(12 * want, s) ||
+    if (nk->zeros(ksz * want, s) || nst->zeros(sizeof(CtState) * lines, s) ||
+        nsum->zeros(4 * lines, s) || nms->zeros(12 * want, s) ||
         (lb.p && nlb->zeros(16 * want, s)) || map.ensure(4 * o) ||
         c->cta_cnt.ensure(4 * CTA_NCNT))
         return -ENOMEM;
     CtState *ost = (CtState *)G.ct_st.p, *ns = (CtState *)nst->p;
     uint32_t *cnt = (uint32_t *)c->cta_cnt.p, moved = 0;
-    const uint64_t other = v6 ? n4 : n6;
-    if ((other && hipMemcpyAsync(v6 ? ns : ns + m4, v6 ? ost : ost + n4, sizeof(CtState) * other,
+    if ((other && hipMemcpyAsync(ns + oth_new, ost + oth_old, sizeof(CtState) * other,
                                  hipMemcpyDeviceToDevice, s) != hipSuccess) ||
         hipMemsetAsync(cnt, 0, 4, s) != hipSuccess ||
-        ct_rehash(v6, key.p, ost + (v6 ? n4 : 0), (const uint4 *)lb.p, o, nk->p,
-                  ns + (v6 ? m4 : 0), (uint4 *)nlb->p, (uint32_t)(want - 1), (uint32_t *)map.p,
-                  cnt, s))
+        ct_rehash(V6, T.key.p, ost + own, (const uint4 *)lb.p, o, nk->p, ns + own,
+                  (uint4 *)nlb->p, (uint32_t)(want - 1), (uint32_t *)map.p, cnt, s))
         return -EIO;
     // the GC log's slots (its deletes the host has not taken)
-    if (!v6 && c->gc_log_used &&
-        ct_remap(&((CtGcRec *)c->gc_log.p)->slot, c->gc_log_used, sizeof(CtGcRec) / 4,
-                 (const uint32_t *)map.p, s))
-        return -EIO;
-    if (v6 && c->gc_log6_used &&
-        ct_remap(&((CtGcRec6 *)c->gc_log6.p)->slot, c->gc_log6_used, sizeof(CtGcRec6) / 4,
-                 (const uint32_t *)map.p, s))
+    using GcRec = typename F::GcRec;
+    if (X.gc_log_used && ct_remap(&((GcRec *)X.gc_log.p)->slot, X.gc_log_used, sizeof(GcRec) / 4,
+                                  (const uint32_t *)map.p, s))
         return -EIO;
     // the host mirror's remap: this one, or composed with one still pending
-    DevBuf &pend = v6 ? G.pend6 : G.pend4;
+    DevBuf &pend = T.pend;
     if (pend.p) {
-        if (ct_remap((uint32_t *)pend.p, v6 ? G.ct6_host.size() : G.ct4_host.size(), 1,
-                     (const uint32_t *)map.p, s))
+        if (ct_remap((uint32_t *)pend.p, T.host.size(), 1, (const uint32_t *)map.p, s))
             return -EIO;
     } else {
         std::swap(pend.p, map.p);
@@ -3760,7 +3431,7 @@ int ct_grow(cfc_ctx *c, bool v6, uint64_t want, hipStream_t s)
     {
         auto old = std::make_shared<Epoch>();
         old->ct = std::make_shared<GCt>();
-        GCt &R = *old->ct;
+        auto &R = tab<V6>(*old->ct);
         auto give = [](DevBuf &from, DevBuf &to, std::unique_ptr<DevBuf> &nb) {
             std::swap(to.p, from.p);
             std::swap(to.bytes, from.bytes);
@@ -3769,12 +3440,12 @@ int ct_grow(cfc_ctx *c, bool v6, uint64_t want, hipStream_t s)
                 std::swap(from.bytes, nb->bytes);
             }
         };
-        give(key, v6 ? R.ct6 : R.ct4, nk);
-        give(G.ct_st, R.ct_st, nst);
-        give(G.ct_sum, R.ct_sum, nsum);
-        give(ms, v6 ? R.ct6_ms : R.ct4_ms, nms);
+        give(T.key, R.key, nk);
+        give(G.ct_st, old->ct->ct_st, nst);
+        give(G.ct_sum, old->ct->ct_sum, nsum);
+        give(T.ms, R.ms, nms);
         if (lb.p)
-            give(lb, v6 ? R.ct6_lb : R.ct4_lb, nlb);
+            give(lb, R.lb, nlb);
         Retired r;
         r.e = old;
         for (hipStream_t st : c->streams) {
@@ -3790,25 +3461,14 @@ int ct_grow(cfc_ctx *c, bool v6, uint64_t want, hipStream_t s)
         }
         c->retired.push_back(std::move(r));
     }
-    if (v6) {
-        G.slots6 = want;
-        G.ct6_mask = (uint32_t)(want - 1);
-        G.ct6_probe = G.ct6_mask;
-        G.tomb6 = moved > G.n_ct6 ? (uint32_t)(moved - G.n_ct6) : 0u;
-        c->ct_used6 = moved;
-        c->ct_used6_valid = true;
-        c->cta_ins6 = 0;
-        c->ct_min6 = std::max<uint64_t>(c->ct_min6, want);
-    } else {
-        G.slots4 = want;
-        G.ct4_mask = (uint32_t)(want - 1);
-        G.ct4_probe = G.ct4_mask;
-        G.tomb4 = moved > G.n_ct4 ? (uint32_t)(moved - G.n_ct4) : 0u;
-        c->ct_used = moved;
-        c->ct_used_valid = true;
-        c->cta_ins = 0;
-        c->ct_min4 = std::max<uint64_t>(c->ct_min4, want);
-    }
+    T.slots = want;
+    T.mask = (uint32_t)(want - 1);
+    T.probe = T.mask;
+    T.tomb = moved > T.n ? (uint32_t)(moved - T.n) : 0u;
+    X.used = moved;
+    X.used_valid = true;
+    X.ins = 0;
+    X.min_slots = std::max<uint64_t>(X.min_slots, want);
     assemble(E);
     E.T.id_cover = c->id_cover;
     // the table moved under every hit slot and summary a launch left
@@ -3827,6 +3487,7 @@ int ct_apply_dev(cfc_ctx *c, const Hdr *in, const cfc_out *out, int mode, uint16
                  hipStream_t s, bool may_grow = true, bool order = true)
 {
     constexpr bool V6 = std::is_same<Hdr, cfc_hdr_v6>::value;
+    using F = CtFamily<V6>;
     settle(c);
     if (c->ct_apply_mode != CFC_CT_APPLY_DEVICE || !c->epoch)
         return 1;
@@ -3845,30 +3506,31 @@ int ct_apply_dev(cfc_ctx *c, const Hdr *in, const cfc_out *out, int mode, uint16
     }
     Epoch &E = *c->epoch;
     GCt &G = *E.ct;
+    auto &T = tab<V6>(G);
+    cfc_ctx::CtFam &X = c->ctf[V6];
     // a load balancer: its per-slot ct_state is on the device (the apply
     // writes it with every create), and an egress batch replays the service
     // step (lb4_local / lb6_local, the egress reply's reverse NAT: k_cta_lb)
     const bool lbt = V6 ? (E.T.lb6 || E.T.rnat6) : (E.T.lb4 || E.T.rnat4);
-    DevBuf &lbst = V6 ? G.ct6_lb : G.ct4_lb;
+    DevBuf &lbst = T.lb;
     if (lbt && !lbst.p)
         return 1;
     const bool lbm = lbt && mode == CFC_MODE_EGRESS;
     const uint64_t k3 = lbm ? 3 : 2;   // requests per header, writes per create
-    const uint64_t n = in->n, slots = V6 ? G.slots6 : G.slots4;
+    const uint64_t n = in->n, slots = T.slots;
     if (!slots && may_grow && n < (1ull << 27)) {
         // no table yet (the family's maps were empty at the build): build
         // one sized for this batch and apply on it — unless other map groups
         // wait for a commit (the tables the batch was classified with)
         bool maps = false, others = false;
         for (auto &kv : c->maps)
-            maps |= kv.second->role == (V6 ? ROLE_CT6 : ROLE_CT4);
+            maps |= kv.second->role == F::role;
         uint64_t sg[NGROUPS];
         group_sigs(c, sg);
         for (int g = 0; g < NGROUPS; g++)
             others |= g != 3 && sg[g] != c->built_sig[g];
         if (maps && !others) {
-            uint64_t &mn = V6 ? c->ct_min6 : c->ct_min4;
-            mn = std::max<uint64_t>({mn, 1ull << 16, 8 * n});
+            X.min_slots = std::max<uint64_t>({X.min_slots, 1ull << 16, 8 * n});
             c->built_sig[3] = ~0ull;
             if (int rc = commit_locked(c, s))
                 return rc;
@@ -3912,21 +3574,15 @@ int ct_apply_dev(cfc_ctx *c, const Hdr *in, const cfc_out *out, int mode, uint16
     A.now = c->now;
     A.seq = c->cta_seq;
     A.nat46 = c->hop_nat46 ? 1u : 0u;
-    if (V6) {
-        A.ct6 = (Ct6Slot *)G.ct6.p;
-        A.mask = G.ct6_mask;
-        A.acct_base = E.T.ct6_acct_base;
-        A.st = (CtState *)G.ct_st.p + A.acct_base;
-        A.ms = (uint2 *)G.ct6_ms.p;
-        A.lh = (uint32_t *)(A.ms + slots);
-    } else {
-        A.ct4 = (Ct4Slot *)G.ct4.p;
-        A.mask = G.ct4_mask;
-        A.acct_base = 0;
-        A.st = (CtState *)G.ct_st.p;
-        A.ms = (uint2 *)G.ct4_ms.p;
-        A.lh = (uint32_t *)(A.ms + slots);
-    }
+    if constexpr (V6)
+        A.ct6 = (Ct6Slot *)T.key.p;
+    else
+        A.ct4 = (Ct4Slot *)T.key.p;
+    A.mask = T.mask;
+    A.acct_base = (uint32_t)state_base<V6>(G);
+    A.st = (CtState *)G.ct_st.p + A.acct_base;
+    A.ms = (uint2 *)T.ms.p;
+    A.lh = (uint32_t *)(A.ms + slots);
     A.hs = (uint32_t *)c->cta_hs.p;
     A.reqA = (uint64_t *)c->cta_req.p;
     A.req_cap = (uint32_t)std::min<uint64_t>(k3 * n, 0xFFFFFFFFu);
@@ -3946,7 +3602,7 @@ int ct_apply_dev(cfc_ctx *c, const Hdr *in, const cfc_out *out, int mode, uint16
     {   // this batch's hit slots from its classify launch, if still there
         // (not with a service step: its tuples may differ from the launch's)
         const auto &L = c->last_cls;
-        if (!lbm && L.valid && L.family == (V6 ? 6 : 4) && L.gen == c->ct_gen && L.ct == out->ct &&
+        if (!lbm && L.valid && L.family == F::family && L.gen == c->ct_gen && L.ct == out->ct &&
             L.saddr == (const void *)in->saddr && L.n == n && L.mode == mode && L.ep == ep_lxc) {
             A.ck1 = (const uint32_t *)((const char *)c->ws + L.k1);
             A.ck2 = L.k2 ? (const uint32_t *)((const char *)c->ws + L.k2) : nullptr;
@@ -4067,15 +3723,10 @@ int ct_apply_dev(cfc_ctx *c, const Hdr *in, const cfc_out *out, int mode, uint16
     // (a sparse scan does not count the plain hits: route's bound is every stage)
     const uint64_t nreqA = hc[CTA_NREQA],
                    nhit = A.sparse ? (mode == CFC_MODE_EGRESS ? 2 * n : n) : hc[CTA_NHIT];
-    uint64_t &claims = V6 ? c->cta_claims6 : c->cta_claims;
-    uint64_t &ins = V6 ? c->cta_ins6 : c->cta_ins;
-    uint64_t &log_used = V6 ? c->log6_used : c->log_used;
-    DevBuf &logbuf = V6 ? c->cta_log6 : c->cta_log;
-    const size_t log_rec = V6 ? sizeof(CtLog6) : sizeof(CtLog);
-    auto used_now = [&]() -> uint64_t {
-        return V6 ? (c->ct_used6_valid ? c->ct_used6 : (uint64_t)G.n_ct6 + G.tomb6)
-                  : (c->ct_used_valid ? c->ct_used : (uint64_t)G.n_ct4 + G.tomb4);
-    };
+    uint64_t &claims = X.claims, &ins = X.ins, &log_used = X.log_used;
+    DevBuf &logbuf = X.log;
+    const size_t log_rec = sizeof(typename F::Log);
+    auto used_now = [&]() -> uint64_t { return X.used_valid ? X.used : T.used(); };
     uint64_t used = used_now();
     const uint64_t nr = std::max<uint64_t>(nreqA, 1);
     const uint64_t cx_cap = nhit + (k3 + 1) * nreqA + 64;   // (round 1 laid out for 2 per create)
@@ -4099,7 +3750,7 @@ int ct_apply_dev(cfc_ctx *c, const Hdr *in, const cfc_out *out, int mode, uint16
     uint64_t newk_kind[2] = {newk, newk};   // [TCP map, ANY map]
     std::vector<Map *> fmaps;               // the family's CT maps
     for (auto &kv : c->maps)
-        if (kv.second->role == (V6 ? ROLE_CT6 : ROLE_CT4))
+        if (kv.second->role == F::role)
             fmaps.push_back(kv.second.get());
     std::vector<uint64_t> newk_map;   // per fmaps[j], once counted exactly
     // the TCP maps' related entries among those keys (saddr, daddr, ct word:
@@ -4167,28 +3818,7 @@ int ct_apply_dev(cfc_ctx *c, const Hdr *in, const cfc_out *out, int mode, uint16
             A.n_emaps = 0;
         }
     }
-    static const bool grow_host = getenv("CFC_CT_GROW_HOST") != nullptr;
-    if (ok && !fits(newk) && may_grow && maps_fit() && grow_host) {
-        // (A/B and debugging only: the old growth — the device state synced
-        // into the maps, the CT group rebuilt larger through a commit —
-        // unless other groups wait for a commit)
-        bool others = false;
-        uint64_t sg[NGROUPS];
-        group_sigs(c, sg);
-        for (int g = 0; g < NGROUPS; g++)
-            others |= g != 3 && sg[g] != c->built_sig[g];
-        if (!others) {
-            uint64_t &mn = V6 ? c->ct_min6 : c->ct_min4;
-            mn = std::max<uint64_t>(mn, 2 * (used + ins + newk));
-            if (hipMemsetAsync(A.ms, 0, 12 * slots, s) != hipSuccess)
-                return -EIO;
-            c->built_sig[3] = ~0ull;
-            if (int rc = commit_locked(c, s))
-                return rc;
-            return ct_apply_dev(c, in, out, mode, ep_lxc, s, false, false);
-        }
-    }
-    if (ok && !fits(newk) && may_grow && maps_fit() && !grow_host) {
+    if (ok && !fits(newk) && may_grow && maps_fit()) {
         // the batch outgrows the table but not its maps: the table grows on
         // the device (ct_grow: at least twice the slots, room for this
         // batch at under half load) and the batch is applied again on it —
@@ -4196,7 +3826,7 @@ int ct_apply_dev(cfc_ctx *c, const Hdr *in, const cfc_out *out, int mode, uint16
         uint64_t want = 2 * slots;
         while (want < 2 * (used + ins + newk))
             want *= 2;
-        const int g = ct_grow(c, V6, want, s);
+        const int g = ct_grow<V6>(c, want, s);
         if (g < 0)
             return g;
         if (g == 0)
@@ -4224,7 +3854,7 @@ int ct_apply_dev(cfc_ctx *c, const Hdr *in, const cfc_out *out, int mode, uint16
         // pair writes is a new key only when the map lacks it
         for (size_t q = 0; q + 2 < tcp_rel.size(); q += 3) {
             const uint32_t w = tcp_rel[q + 2].x;
-            const size_t al = V6 ? 16 : 4;
+            const size_t al = F::al;
             char k[38];
             const uint32_t z = 0;
             memcpy(k, &tcp_rel[q], al);
@@ -4232,7 +3862,7 @@ int ct_apply_dev(cfc_ctx *c, const Hdr *in, const cfc_out *out, int mode, uint16
             memcpy(k + 2 * al, &z, 4);
             k[2 * al + 4] = (char)(w & 0xFF);
             k[2 * al + 5] = (char)((w >> 8) & 7);
-            auto mit = G.ct_maps.find(ct_map_key(V6 ? 6 : 4, w & ~0x7FFu, 0));
+            auto mit = G.ct_maps.find(ct_map_key(F::family, w & ~0x7FFu, 0));
             if (mit == G.ct_maps.end())
                 continue;
             for (size_t j = 0; j < fmaps.size(); j++)
@@ -4248,7 +3878,7 @@ int ct_apply_dev(cfc_ctx *c, const Hdr *in, const cfc_out *out, int mode, uint16
             const uint64_t nk = lbm ? 4 * n : mode == CFC_MODE_EGRESS ? 2 * n : n;
             if (A.sparse && cta_hs_fill(A, s))   // (the protect pass reads hs)
                 return -EIO;
-            const int rc = ct_evict_maps(c, V6, fmaps, want, A.hs, nk, s);
+            const int rc = ct_evict_maps<V6>(c, fmaps, want, A.hs, nk, s);
             if (rc < 0)
                 return rc;
             if (rc == 2)   // (evicted on the host, not patched in: the host path)
@@ -4291,7 +3921,7 @@ int ct_apply_dev(cfc_ctx *c, const Hdr *in, const cfc_out *out, int mode, uint16
     A.log_cap = (uint32_t)(logbuf.bytes / log_rec - log_used);
     // from here the device table changes: the host mirror lags until ct_sync
     c->ct_dirty = true;
-    c->ct6_dirty |= V6;
+    c->ctf[1].dirty |= V6;
     // (no wait for the fold: the host's bookkeeping below was read after
     // route, the rest is stream-ordered before anything that reads the table)
     if (early && hc[CTA_NCX] > nroute_cap)
@@ -4779,71 +4409,93 @@ struct GcFilterHost {
     }
 };
 
-// the IPv4 part on the device: the CT table and the pending CtLog
+// one family's part on the device (doGC4 / doGC6, ctmap.go:239): its CT
+// table and its pending log (k_ct_gc<V6>: an IPv6 slot's addresses are read
+// only for the selected maps' entries)
+template <bool V6>
 int ct_gc_dev(cfc_ctx *c, const std::vector<Map *> &sel, const cfc_ct_gc_filter &f,
-              cfc_ct_gc_stats &st, hipStream_t s, const uint32_t *protect)
+              cfc_ct_gc_stats &st, hipStream_t s)
 {
+    using F = CtFamily<V6>;
+    using Addr = typename F::Addr;
+    using GcRec = typename F::GcRec;
+    using Log = typename F::Log;
     settle(c);
     Epoch &E = *c->epoch;
     GCt &G = *E.ct;
-    const uint64_t slots = G.slots4;
-    // the selected maps' selector words, and the IPv4 addresses of the sets
+    auto &T = tab<V6>(G);
+    cfc_ctx::CtFam &X = c->ctf[V6];
+    const uint64_t slots = T.slots;
+    // the selected maps' selector words, and the family's addresses of the sets
     std::vector<uint32_t> mw;
     std::vector<Map *> mm;
     for (Map *m : sel)
-        if (m->role == ROLE_CT4) {
+        if (m->role == F::role) {
             mw.push_back(ct_owner_word((uint32_t)std::max(m->policy_lxc, 0), m->policy_lxc >= 0) |
                          (m->ct_any ? 2u : 0u));
             mm.push_back(m);
         }
-    if (mw.empty())
+    if (mw.empty() || !slots)
         return 0;
-    auto v4set = [](const cfc_ip *set, uint32_t n) {
-        std::vector<uint32_t> v;
+    auto famset = [](const cfc_ip *set, uint32_t n) {
+        std::vector<Addr> v;
         for (uint32_t i = 0; i < n; i++)
-            if (set[i].family == 4) {
-                uint32_t a;
-                memcpy(&a, set[i].addr, 4);
+            if (set[i].family == F::family) {
+                Addr a;
+                memcpy(&a, set[i].addr, F::al);
                 v.push_back(a);
             }
-        std::sort(v.begin(), v.end());
+        std::sort(v.begin(), v.end(), F::addr_less);
         return v;
     };
-    const std::vector<uint32_t> va = (f.flags & CFC_GC_VALID_IPS) ? v4set(f.valid_ips, f.n_valid)
-                                                                   : std::vector<uint32_t>();
-    const std::vector<uint32_t> ma = (f.flags & CFC_GC_MATCH_IPS) ? v4set(f.match_ips, f.n_match)
-                                                                   : std::vector<uint32_t>();
+    const std::vector<Addr> va = (f.flags & CFC_GC_VALID_IPS) ? famset(f.valid_ips, f.n_valid)
+                                                               : std::vector<Addr>();
+    const std::vector<Addr> ma = (f.flags & CFC_GC_MATCH_IPS) ? famset(f.match_ips, f.n_match)
+                                                               : std::vector<Addr>();
     // every entry the host mirror holds can be deleted once before its next
     // sync (one the host never saw needs no log record): the log's room
-    const uint64_t need = c->gc_log_used + G.n_ct4 + 1;
-    if (c->gc_log.bytes < sizeof(CtGcRec) * need) {
+    const uint64_t need = X.gc_log_used + T.n + 1;
+    if (X.gc_log.bytes < sizeof(GcRec) * need) {
         DevBuf nl;
-        if (nl.ensure(sizeof(CtGcRec) * need))
+        if (nl.ensure(sizeof(GcRec) * need))
             return -ENOMEM;
-        if (c->gc_log_used &&
-            (hipMemcpyAsync(nl.p, c->gc_log.p, sizeof(CtGcRec) * c->gc_log_used,
+        if (X.gc_log_used &&
+            (hipMemcpyAsync(nl.p, X.gc_log.p, sizeof(GcRec) * X.gc_log_used,
                             hipMemcpyDeviceToDevice, s) != hipSuccess ||
              hipStreamSynchronize(s) != hipSuccess))
             return -EIO;
-        std::swap(nl.p, c->gc_log.p);
-        std::swap(nl.bytes, c->gc_log.bytes);
+        std::swap(nl.p, X.gc_log.p);
+        std::swap(nl.bytes, X.gc_log.bytes);
     }
-    const size_t set_words = CTG_MAX_MAPS * 2 + va.size() + ma.size() + 1;
-    if (c->gc_sets.ensure(4 * set_words) || c->gc_cnt.ensure(4 * CTG_NCNT) ||
-        (c->log_used && c->gc_tmp.ensure(sizeof(CtLog) * c->log_used)))
+    // sets: the maps' words (2 * CTG_MAX_MAPS u32), then the addresses
+    // (u32 or uint4) from that same offset
+    const size_t set_bytes = 8 * CTG_MAX_MAPS + sizeof(Addr) * (va.size() + ma.size() + 1);
+    if (c->gc_sets.ensure(set_bytes) || c->gc_cnt.ensure(4 * CTG_NCNT) ||
+        (X.log_used && c->gc_tmp.ensure(sizeof(Log) * X.log_used)))
         return -ENOMEM;
     uint32_t *sets = (uint32_t *)c->gc_sets.p, *cnt = (uint32_t *)c->gc_cnt.p;
+    Addr *dev_addrs = (Addr *)(sets + 2 * CTG_MAX_MAPS);
     uint64_t deleted = 0, fresh = 0, live = 0, nonfree = 0, freed = 0, last_freed = 0;
-    uint32_t logkept = (uint32_t)c->log_used, logn = (uint32_t)c->log_used;
+    uint32_t logkept = (uint32_t)X.log_used, logn = (uint32_t)X.log_used;
     for (size_t a = 0; a < mw.size(); a += CTG_MAX_MAPS) {
         const uint32_t nm = (uint32_t)std::min<size_t>(CTG_MAX_MAPS, mw.size() - a);
         std::vector<uint32_t> hs(CTG_MAX_MAPS * 2, 0);
         std::copy(mw.begin() + (long)a, mw.begin() + (long)a + nm, hs.begin());
-        hs.insert(hs.end(), va.begin(), va.end());
-        hs.insert(hs.end(), ma.begin(), ma.end());
-        CtGcArgs A{};
-        A.ct4 = (Ct4Slot *)G.ct4.p;
-        A.st = (CtState *)G.ct_st.p;
+        std::vector<Addr> addrs(va);
+        addrs.insert(addrs.end(), ma.begin(), ma.end());
+        CtGcArgs A{};   // (protect stays null: no slot is exempt)
+        if constexpr (V6) {
+            A.ct6 = (Ct6Slot *)T.key.p;
+            A.valid6 = dev_addrs;
+            A.match6 = dev_addrs + va.size();
+            A.log6 = (GcRec *)X.gc_log.p + X.gc_log_used + deleted;
+        } else {
+            A.ct4 = (Ct4Slot *)T.key.p;
+            A.valid = dev_addrs;
+            A.match = dev_addrs + va.size();
+            A.log = (GcRec *)X.gc_log.p + X.gc_log_used + deleted;
+        }
+        A.st = (CtState *)G.ct_st.p + state_base<V6>(G);
         A.slots = slots;
         A.mask = (uint32_t)(slots - 1);
         A.maps = sets;
@@ -4853,24 +4505,23 @@ int ct_gc_dev(cfc_ctx *c, const std::vector<Map *> &sel, const cfc_ct_gc_filter 
                   ((f.flags & CFC_GC_VALID_IPS) ? CTG_VALID : 0u) |
                   ((f.flags & CFC_GC_MATCH_IPS) ? CTG_MATCH : 0u);
         A.time = f.time;
-        A.valid = sets + 2 * CTG_MAX_MAPS;
         A.n_valid = (uint32_t)va.size();
-        A.match = A.valid + va.size();
         A.n_match = (uint32_t)ma.size();
-        A.log = (CtGcRec *)c->gc_log.p + c->gc_log_used + deleted;
-        A.log_cap = (uint32_t)(c->gc_log.bytes / sizeof(CtGcRec) - c->gc_log_used - deleted);
+        A.log_cap = (uint32_t)(X.gc_log.bytes / sizeof(GcRec) - X.gc_log_used - deleted);
         A.cnt = cnt;
-        A.protect = protect;
         uint32_t hc[CTG_NCNT], hm[CTG_MAX_MAPS];
         if (hipMemcpyAsync(sets, hs.data(), 4 * hs.size(), hipMemcpyHostToDevice, s) !=
                 hipSuccess ||
-            hipMemsetAsync(cnt, 0, 4 * CTG_NCNT, s) != hipSuccess || ct_gc4(A, s))
+            (!addrs.empty() &&
+             hipMemcpyAsync(dev_addrs, addrs.data(), sizeof(Addr) * addrs.size(),
+                            hipMemcpyHostToDevice, s) != hipSuccess) ||
+            hipMemsetAsync(cnt, 0, 4 * CTG_NCNT, s) != hipSuccess || ct_gc_launch(A, s))
             return -EIO;
         // the pending TCP-map ICMP entries of the applies, compacted (all
         // logn places copied back: the kept ones lead, the rest is past the
         // new count — no wait for that count first)
-        if (logn && (ct_gc_log(A, (const CtLog *)c->cta_log.p, logn, (CtLog *)c->gc_tmp.p, s) ||
-                     hipMemcpyAsync(c->cta_log.p, c->gc_tmp.p, sizeof(CtLog) * logn,
+        if (logn && (ct_gc_log(A, (const Log *)X.log.p, logn, (Log *)c->gc_tmp.p, s) ||
+                     hipMemcpyAsync(X.log.p, c->gc_tmp.p, sizeof(Log) * logn,
                                     hipMemcpyDeviceToDevice, s) != hipSuccess))
             return -EIO;
         if (hipMemcpyAsync(hc, cnt, 4 * CTG_NCNT, hipMemcpyDeviceToHost, s) != hipSuccess ||
@@ -4892,154 +4543,23 @@ int ct_gc_dev(cfc_ctx *c, const std::vector<Map *> &sel, const cfc_ct_gc_filter 
             logn = logkept;
         }
     }
-    c->gc_log_used += deleted;
-    c->cta_claims -= std::min(c->cta_claims, fresh);
+    X.gc_log_used += deleted;
+    X.claims -= std::min(X.claims, fresh);
     // exact occupancy now: the non-free slots the last pass saw, less what
     // its trim freed (an earlier chunk's deletes are tombstones it counted)
-    c->ct_used = nonfree >= last_freed ? nonfree - last_freed : 0;
-    c->cta_ins = 0;
-    c->ct_used_valid = true;
-    if (deleted || fresh)
-        c->ct_dirty = true;
-    c->ct_gen++;   // the table changed under any classify launch's hit slots
-    st.device_deleted += deleted + fresh;
-    st.log_deleted += c->log_used - logkept;
-    st.alive += live + logkept;
-    st.slots_freed += freed;
-    c->log_used = logkept;
-    return 0;
-}
-
-// the IPv6 part on the device (doGC6, ctmap.go:239): the CT6 table and the
-// pending CtLog6 — the same passes as ct_gc_dev (k_ct_gc<true>), a slot's
-// addresses read only for the selected maps' entries
-int ct_gc_dev6(cfc_ctx *c, const std::vector<Map *> &sel, const cfc_ct_gc_filter &f,
-               cfc_ct_gc_stats &st, hipStream_t s)
-{
-    settle(c);
-    Epoch &E = *c->epoch;
-    GCt &G = *E.ct;
-    const uint64_t slots = G.slots6;
-    std::vector<uint32_t> mw;
-    std::vector<Map *> mm;
-    for (Map *m : sel)
-        if (m->role == ROLE_CT6) {
-            mw.push_back(ct_owner_word((uint32_t)std::max(m->policy_lxc, 0), m->policy_lxc >= 0) |
-                         (m->ct_any ? 2u : 0u));
-            mm.push_back(m);
-        }
-    if (mw.empty() || !slots)
-        return 0;
-    auto v6set = [](const cfc_ip *set, uint32_t n) {
-        std::vector<uint4> v;
-        for (uint32_t i = 0; i < n; i++)
-            if (set[i].family == 6) {
-                uint4 a;
-                memcpy(&a, set[i].addr, 16);
-                v.push_back(a);
-            }
-        std::sort(v.begin(), v.end(), [](const uint4 &a, const uint4 &b) {
-            return a.x != b.x ? a.x < b.x : a.y != b.y ? a.y < b.y : a.z != b.z ? a.z < b.z
-                                                                                : a.w < b.w;
-        });
-        return v;
-    };
-    const std::vector<uint4> va = (f.flags & CFC_GC_VALID_IPS) ? v6set(f.valid_ips, f.n_valid)
-                                                                : std::vector<uint4>();
-    const std::vector<uint4> ma = (f.flags & CFC_GC_MATCH_IPS) ? v6set(f.match_ips, f.n_match)
-                                                                : std::vector<uint4>();
-    const uint64_t need = c->gc_log6_used + G.n_ct6 + 1;
-    if (c->gc_log6.bytes < sizeof(CtGcRec6) * need) {
-        DevBuf nl;
-        if (nl.ensure(sizeof(CtGcRec6) * need))
-            return -ENOMEM;
-        if (c->gc_log6_used &&
-            (hipMemcpyAsync(nl.p, c->gc_log6.p, sizeof(CtGcRec6) * c->gc_log6_used,
-                            hipMemcpyDeviceToDevice, s) != hipSuccess ||
-             hipStreamSynchronize(s) != hipSuccess))
-            return -EIO;
-        std::swap(nl.p, c->gc_log6.p);
-        std::swap(nl.bytes, c->gc_log6.bytes);
-    }
-    // sets: the maps' words (2 * CTG_MAX_MAPS u32), then the addresses (uint4)
-    const size_t set_bytes = 8 * CTG_MAX_MAPS + 16 * (va.size() + ma.size() + 1);
-    if (c->gc_sets.ensure(set_bytes) || c->gc_cnt.ensure(4 * CTG_NCNT) ||
-        (c->log6_used && c->gc_tmp.ensure(sizeof(CtLog6) * c->log6_used)))
-        return -ENOMEM;
-    uint32_t *sets = (uint32_t *)c->gc_sets.p, *cnt = (uint32_t *)c->gc_cnt.p;
-    uint64_t deleted = 0, fresh = 0, live = 0, nonfree = 0, freed = 0, last_freed = 0;
-    uint32_t logkept = (uint32_t)c->log6_used, logn = (uint32_t)c->log6_used;
-    for (size_t a = 0; a < mw.size(); a += CTG_MAX_MAPS) {
-        const uint32_t nm = (uint32_t)std::min<size_t>(CTG_MAX_MAPS, mw.size() - a);
-        std::vector<uint32_t> hs(CTG_MAX_MAPS * 2, 0);
-        std::copy(mw.begin() + (long)a, mw.begin() + (long)a + nm, hs.begin());
-        std::vector<uint4> addrs(va);
-        addrs.insert(addrs.end(), ma.begin(), ma.end());
-        CtGcArgs A{};
-        A.ct6 = (Ct6Slot *)G.ct6.p;
-        A.st = (CtState *)G.ct_st.p + G.slots4;
-        A.slots = slots;
-        A.mask = (uint32_t)(slots - 1);
-        A.maps = sets;
-        A.n_maps = nm;
-        A.mcnt = sets + CTG_MAX_MAPS;
-        A.flags = ((f.flags & CFC_GC_REMOVE_EXPIRED) ? CTG_REMOVE_EXPIRED : 0u) |
-                  ((f.flags & CFC_GC_VALID_IPS) ? CTG_VALID : 0u) |
-                  ((f.flags & CFC_GC_MATCH_IPS) ? CTG_MATCH : 0u);
-        A.time = f.time;
-        A.valid6 = (const uint4 *)(sets + 2 * CTG_MAX_MAPS);
-        A.n_valid = (uint32_t)va.size();
-        A.match6 = A.valid6 + va.size();
-        A.n_match = (uint32_t)ma.size();
-        A.log6 = (CtGcRec6 *)c->gc_log6.p + c->gc_log6_used + deleted;
-        A.log_cap = (uint32_t)(c->gc_log6.bytes / sizeof(CtGcRec6) - c->gc_log6_used - deleted);
-        A.cnt = cnt;
-        uint32_t hc[CTG_NCNT], hm[CTG_MAX_MAPS];
-        if (hipMemcpyAsync(sets, hs.data(), 4 * hs.size(), hipMemcpyHostToDevice, s) !=
-                hipSuccess ||
-            (!addrs.empty() &&
-             hipMemcpyAsync(sets + 2 * CTG_MAX_MAPS, addrs.data(), 16 * addrs.size(),
-                            hipMemcpyHostToDevice, s) != hipSuccess) ||
-            hipMemsetAsync(cnt, 0, 4 * CTG_NCNT, s) != hipSuccess || ct_gc4(A, s))
-            return -EIO;
-        if (logn && (ct_gc_log6(A, (const CtLog6 *)c->cta_log6.p, logn, (CtLog6 *)c->gc_tmp.p, s) ||
-                     hipMemcpyAsync(c->cta_log6.p, c->gc_tmp.p, sizeof(CtLog6) * logn,
-                                    hipMemcpyDeviceToDevice, s) != hipSuccess))
-            return -EIO;
-        if (hipMemcpyAsync(hc, cnt, 4 * CTG_NCNT, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipMemcpyAsync(hm, A.mcnt, 4 * nm, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess)
-            return -EIO;
-        if (hc[CTG_DELETED] > A.log_cap)
-            return -EIO;
-        for (uint32_t j = 0; j < nm; j++)
-            mm[a + j]->gc_pending += hm[j];
-        deleted += hc[CTG_DELETED];
-        fresh += hc[CTG_FRESH];
-        live += hc[CTG_LIVE];
-        nonfree = hc[CTG_NONFREE];
-        freed += hc[CTG_FREED];
-        last_freed = hc[CTG_FREED];
-        if (logn) {
-            logkept = hc[CTG_LOGKEPT];
-            logn = logkept;
-        }
-    }
-    c->gc_log6_used += deleted;
-    c->cta_claims6 -= std::min(c->cta_claims6, fresh);
-    c->ct_used6 = nonfree >= last_freed ? nonfree - last_freed : 0;
-    c->cta_ins6 = 0;
-    c->ct_used6_valid = true;
+    X.used = nonfree >= last_freed ? nonfree - last_freed : 0;
+    X.ins = 0;
+    X.used_valid = true;
     if (deleted || fresh) {
         c->ct_dirty = true;
-        c->ct6_dirty = true;
+        c->ctf[1].dirty |= V6;
     }
-    c->ct_gen++;
+    c->ct_gen++;   // the table changed under any classify launch's hit slots
     st.device_deleted += deleted + fresh;
-    st.log_deleted += c->log6_used - logkept;
+    st.log_deleted += X.log_used - logkept;
     st.alive += live + logkept;
     st.slots_freed += freed;
-    c->log6_used = logkept;
+    X.log_used = logkept;
     return 0;
 }
 
@@ -5069,21 +4589,21 @@ int ct_gc(cfc_ctx *c, int fd, const cfc_ct_gc_filter *f, cfc_ct_gc_stats *out, h
     order_after_launches(c, s);
     cfc_ct_gc_stats st{};
     Epoch &E = *c->epoch;
-    const bool dev4 = E.ct->slots4 && E.ct->ct_st.p, dev6 = E.ct->slots6 && E.ct->ct_st.p;
+    const bool dev4 = E.ct->t4.slots && E.ct->ct_st.p, dev6 = E.ct->t6.slots && E.ct->ct_st.p;
     // both families on the device (doGC4 / doGC6); an IPv6 map without a
     // device table is collected on the host after its device applies are
     // synchronised (their pending-log entries first)
     bool v6host = false;
     for (Map *m : sel)
         v6host |= m->role == ROLE_CT6 && !m->kv.empty() && !dev6;
-    if (v6host && c->ct6_dirty)
+    if (v6host && c->ctf[1].dirty)
         if (int rc = ct_sync(c, s))
             return rc;
     if (dev4)
-        if (int rc = ct_gc_dev(c, sel, *f, st, s, nullptr))
+        if (int rc = ct_gc_dev<false>(c, sel, *f, st, s))
             return rc;
     if (dev6)
-        if (int rc = ct_gc_dev6(c, sel, *f, st, s))
+        if (int rc = ct_gc_dev<true>(c, sel, *f, st, s))
             return rc;
     // what only the host holds: maps without a device table, the TCP maps'
     // ICMP entries (no lookup reaches them: not in the device table)

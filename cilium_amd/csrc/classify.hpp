@@ -462,15 +462,15 @@ int cta_route(const CtaArgs &A, hipStream_t s);
 // 1 << 31 in pad
 int cta_collect(const Ct4Slot *ct4, CtState *st, const uint4 *lb, uint64_t slots,
                 CtSyncRec *out, uint32_t cap, uint32_t *cnt, hipStream_t s);
-int cta_collect6(const Ct6Slot *ct6, CtState *st, const uint4 *lb, uint64_t slots,
-                 CtSyncRec6 *out, uint32_t cap, uint32_t *cnt, hipStream_t s);
+int cta_collect(const Ct6Slot *ct6, CtState *st, const uint4 *lb, uint64_t slots,
+                CtSyncRec6 *out, uint32_t cap, uint32_t *cnt, hipStream_t s);
 int cta_tomb(Ct4Slot *ct4, const CtSyncRec *rec, uint32_t n, hipStream_t s);
-// the IPv4 table's slots that are not free (live, tombstone or claimed),
+// a table's slots that are not free (live, tombstone or claimed),
 // added into *cnt (the exact load: the GC's trim frees tombstones the host
 // mirror still counts)
-int ct_count_nonfree4(const Ct4Slot *ct4, uint64_t slots, uint32_t *cnt, hipStream_t s);
-int ct_count_nonfree6(const Ct6Slot *ct6, uint64_t slots, uint32_t *cnt, hipStream_t s);
-int cta_tomb6(Ct6Slot *ct6, const CtSyncRec6 *rec, uint32_t n, hipStream_t s);
+int ct_count_nonfree(const Ct4Slot *ct4, uint64_t slots, uint32_t *cnt, hipStream_t s);
+int ct_count_nonfree(const Ct6Slot *ct6, uint64_t slots, uint32_t *cnt, hipStream_t s);
+int cta_tomb(Ct6Slot *ct6, const CtSyncRec6 *rec, uint32_t n, hipStream_t s);
 // device-side growth (ct_grow): every key-holding slot of the old table
 // (ok: Ct4Slot / Ct6Slot, oslots) into the new one (nk, nmask + 1 slots,
 // zeroed), with its CtState line (ost -> nst) and LB word (olb -> nlb, when
@@ -527,7 +527,7 @@ struct CtGcArgs {
     uint32_t *cnt;                // CTG_* counters
     const uint32_t *protect;      // slots never deleted (one bit each), or null
 };
-int ct_gc4(const CtGcArgs &A, hipStream_t s);
+int ct_gc_launch(const CtGcArgs &A, hipStream_t s);   // A.ct4 or A.ct6
 // Eviction at a CT map's capacity (cfc_ct_apply, cfc_api.cpp ct_evict_maps):
 // the slots a batch's lookups hit (hs: nk hit-slot words, HS_NONE none) as
 // bits in bm (never evicted)
@@ -536,7 +536,7 @@ int ct_protect_hits(const uint32_t *hs, uint64_t nk, uint32_t *bm, hipStream_t s
 // same way, kept in order of appearance: in[0, n) -> out; the kept count
 // into A.cnt[CTG_LOGKEPT]
 int ct_gc_log(const CtGcArgs &A, const CtLog *in, uint32_t n, CtLog *out, hipStream_t s);
-int ct_gc_log6(const CtGcArgs &A, const CtLog6 *in, uint32_t n, CtLog6 *out, hipStream_t s);
+int ct_gc_log(const CtGcArgs &A, const CtLog6 *in, uint32_t n, CtLog6 *out, hipStream_t s);
 
 // ---- service load balancing of an egress batch (lb.hip)
 struct LbArgs {

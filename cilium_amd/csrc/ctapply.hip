@@ -2928,15 +2928,15 @@ int cta_collect(const Ct4Slot *ct4, CtState *st, const uint4 *lb, uint64_t slots
     return hipGetLastError() == hipSuccess ? 0 : -EIO;
 }
 
-int cta_collect6(const Ct6Slot *ct6, CtState *st, const uint4 *lb, uint64_t slots,
-                 CtSyncRec6 *out, uint32_t cap, uint32_t *cnt, hipStream_t s)
+int cta_collect(const Ct6Slot *ct6, CtState *st, const uint4 *lb, uint64_t slots,
+                CtSyncRec6 *out, uint32_t cap, uint32_t *cnt, hipStream_t s)
 {
     hipLaunchKernelGGL(k_cta_collect<true>, dim3(blocks_for(slots, 8192)), dim3(256), 0, s, ct6,
                        st, lb, slots, out, cap, cnt);
     return hipGetLastError() == hipSuccess ? 0 : -EIO;
 }
 
-int ct_gc4(const CtGcArgs &A, hipStream_t s)
+int ct_gc_launch(const CtGcArgs &A, hipStream_t s)
 {
     if (!A.slots || A.n_maps > CTG_MAX_MAPS)
         return -EINVAL;
@@ -2959,7 +2959,7 @@ int ct_gc_log(const CtGcArgs &A, const CtLog *in, uint32_t n, CtLog *out, hipStr
     return hipGetLastError() == hipSuccess ? 0 : -EIO;
 }
 
-int ct_gc_log6(const CtGcArgs &A, const CtLog6 *in, uint32_t n, CtLog6 *out, hipStream_t s)
+int ct_gc_log(const CtGcArgs &A, const CtLog6 *in, uint32_t n, CtLog6 *out, hipStream_t s)
 {
     if (A.n_maps > CTG_MAX_MAPS)
         return -EINVAL;
@@ -2969,7 +2969,7 @@ int ct_gc_log6(const CtGcArgs &A, const CtLog6 *in, uint32_t n, CtLog6 *out, hip
     return hipGetLastError() == hipSuccess ? 0 : -EIO;
 }
 
-int ct_count_nonfree6(const Ct6Slot *ct6, uint64_t slots, uint32_t *cnt, hipStream_t s)
+int ct_count_nonfree(const Ct6Slot *ct6, uint64_t slots, uint32_t *cnt, hipStream_t s)
 {
     if (slots)
         hipLaunchKernelGGL(k_ct_nonfree<Ct6Slot>, dim3(blocks_for(slots, 2048)), dim3(256), 0, s,
@@ -2977,7 +2977,7 @@ int ct_count_nonfree6(const Ct6Slot *ct6, uint64_t slots, uint32_t *cnt, hipStre
     return hipGetLastError() == hipSuccess ? 0 : -EIO;
 }
 
-int ct_count_nonfree4(const Ct4Slot *ct4, uint64_t slots, uint32_t *cnt, hipStream_t s)
+int ct_count_nonfree(const Ct4Slot *ct4, uint64_t slots, uint32_t *cnt, hipStream_t s)
 {
     if (slots)
         hipLaunchKernelGGL(k_ct_nonfree<Ct4Slot>, dim3(blocks_for(slots, 2048)), dim3(256), 0, s, ct4,
@@ -3031,7 +3031,7 @@ int cta_tomb(Ct4Slot *ct4, const CtSyncRec *rec, uint32_t n, hipStream_t s)
     return hipGetLastError() == hipSuccess ? 0 : -EIO;
 }
 
-int cta_tomb6(Ct6Slot *ct6, const CtSyncRec6 *rec, uint32_t n, hipStream_t s)
+int cta_tomb(Ct6Slot *ct6, const CtSyncRec6 *rec, uint32_t n, hipStream_t s)
 {
     if (n)
         hipLaunchKernelGGL(k_cta_tomb6, dim3((n + 255) / 256), dim3(256), 0, s, ct6, rec, n);

@@ -15,8 +15,212 @@
 #include "flatten.hpp"
 #include "maps.hpp"
 #include "selfcut.hpp"
+#include "ctmirror.hpp"
 
 using namespace cfc;
+
+// ---- the replay of the device's CT records into the host mirror and the CT
+// maps (ctmirror.hpp ct_replay), per family: a 16-slot mirror, the global
+// TCP and ANY maps, hand-written records
+template <bool V6>
+struct ReplayCase {
+    using F = CtFamily<V6>;
+    using Rec = typename F::SyncRec;
+    CtTab<typename F::Slot> T;
+    Map tcp, any;
+    CtMaps maps;
+    int fail = 0;
+    ReplayCase()
+    {
+        T.host.resize(16);
+        T.slots = 16;
+        T.mask = 15;
+        for (Map *m : {&tcp, &any}) {
+            m->role = F::role;
+            m->type = MT_HASH;
+            m->ksz = 2 * F::al + 6;
+            m->vsz = 56;
+            m->max_entries = 64;
+        }
+        any.ct_any = 1;
+        maps[ct_map_key(F::family, 0, 0)] = &tcp;
+        maps[ct_map_key(F::family, 0, 1)] = &any;
+    }
+    // address a of a test tuple: one word (IPv4), four (IPv6)
+    static void addr(uint32_t a, uint32_t out[4])
+    {
+        for (int i = 0; i < 4; i++)
+            out[i] = a + 0x01010101u * (uint32_t)i;
+    }
+    // the map key of tuple (d, s, z, nexthdr, flags), written out by hand
+    static std::string mapkey(uint32_t d, uint32_t s, uint32_t z, uint8_t nh, uint8_t fl)
+    {
+        uint32_t da[4], sa[4];
+        addr(d, da);
+        addr(s, sa);
+        std::string k((const char *)da, F::al);
+        k.append((const char *)sa, F::al);
+        k.append((const char *)&z, 4);
+        k.push_back((char)nh);
+        k.push_back((char)fl);
+        return k;
+    }
+    template <class R>   // a sync or GC record's key fields
+    static void setkey(R &r, uint32_t d, uint32_t s, uint32_t z, uint32_t w)
+    {
+        uint32_t da[4], sa[4];
+        addr(d, da);
+        addr(s, sa);
+        if constexpr (V6) {
+            memcpy(&r.d, da, 16);
+            memcpy(&r.s, sa, 16);
+        } else {
+            r.x = da[0];
+            r.y = sa[0];
+        }
+        r.z = z;
+        r.w = w;
+    }
+    static Rec rec(uint32_t slot, uint32_t d, uint32_t s, uint32_t z, uint32_t w, uint32_t dirty,
+                   uint32_t rev, uint32_t sec)
+    {
+        Rec r{};
+        r.slot = slot;
+        setkey(r, d, s, z, w);
+        r.info.sec = sec;
+        r.info.y = rev | dirty;
+        return r;
+    }
+    static typename F::Log logrec(uint32_t sa, uint32_t da, uint32_t seq, uint32_t order,
+                                  uint32_t sec)
+    {
+        typename F::Log g{};
+        uint32_t a[4];
+        addr(sa, a);
+        memcpy(&g.x, a, F::al);
+        addr(da, a);
+        memcpy(&g.y, a, F::al);
+        g.w = ct_word(V6 ? 58 : 1, 0, 0);
+        g.now = 1000;
+        g.dirlen = 1u << 31 | 84;
+        g.seq = seq;
+        g.order = order;
+        g.sec = sec;
+        return g;
+    }
+    void replay(const std::vector<typename F::GcRec> &gc, const std::vector<Rec> &rs,
+                std::vector<typename F::Log> lg = {})
+    {
+        ct_replay<V6>(T, maps, gc, rs, lg);
+    }
+    template <class V>
+    static V at(const std::string &v, size_t off)
+    {
+        V x;
+        memcpy(&x, &v[off], sizeof(V));
+        return x;
+    }
+    void expect(bool ok, const char *what)
+    {
+        if (!ok) {
+            printf("ct_replay v%d %s FAIL (n %u, tomb %u)\n", F::family, what, T.n, T.tomb);
+            fail = 1;
+        }
+    }
+    int run()
+    {
+        const uint32_t W = ct_word(6, 1, 0), Z = 0x00500400u;
+        const std::string K = mapkey(10, 20, Z, 6, 1);
+        // create: every field ct_value_from_dev writes
+        Rec c = rec(3, 10, 20, Z, W, CTI_CREATED, 7, 0x1234);
+        c.last_rx = 11;
+        c.last_tx = 12;
+        c.flags = 2u << 16 | CTT_NON_SYN | 0xAB << 8 | 0xCD;
+        c.lifetime = 1060;
+        replay({}, {c});
+        const std::string *v = tcp.kv.count(K) ? &tcp.kv[K].val : nullptr;
+        expect(v && v->size() == 56 && any.kv.empty() && T.n == 1 && T.tomb == 0, "create");
+        expect(v && at<uint32_t>(*v, 32) == 1060 && at<uint16_t>(*v, 36) == (2 | 16) &&
+                   at<uint16_t>(*v, 38) == 7 && at<uint16_t>(*v, 40) == 0 &&
+                   (uint8_t)(*v)[42] == 0xAB && (uint8_t)(*v)[43] == 0xCD &&
+                   at<uint32_t>(*v, 44) == 0x1234 && at<uint32_t>(*v, 48) == 12 &&
+                   at<uint32_t>(*v, 52) == 11,
+               "create value");
+        expect(ct_key_eq<V6>(F::key(T.host[3]), F::key(c)), "create mirror");
+        // update: rev_nat_index and src_sec_id stay; then the LB state in pad
+        Rec u = rec(3, 10, 20, Z, W, CTI_UPDATED, 99, 0x9999);
+        u.flags = 1u << 16 | CTT_NAT46;
+        u.lifetime = 2000;
+        replay({}, {u});
+        v = &tcp.kv[K].val;
+        expect(at<uint32_t>(*v, 32) == 2000 && at<uint16_t>(*v, 36) == (1 | 4) &&
+                   at<uint16_t>(*v, 38) == 7 && at<uint32_t>(*v, 44) == 0x1234 && T.n == 1,
+               "update");
+        u.pad = 1u << 31 | 1u << 16 | 0x55;
+        replay({}, {u});
+        expect(at<uint16_t>(*v, 36) == (1 | 4 | 8) && at<uint16_t>(*v, 40) == 0x55, "update lb");
+        // deleted and created again in another slot, the create listed first
+        Rec d = rec(3, 10, 20, Z, W | CT_TOMBSTONE, CTI_DELETED, 0, 0);
+        Rec c2 = rec(5, 10, 20, Z, W, CTI_CREATED, 8, 0x4321);
+        replay({}, {c2, d});
+        expect(tcp.kv.count(K) && at<uint16_t>(tcp.kv[K].val, 38) == 8 && T.n == 1 &&
+                   T.tomb == 1 && T.host[3].w == CT_TOMBSTONE &&
+                   ct_key_eq<V6>(F::key(T.host[5]), F::key(c2)),
+               "delete, re-create");
+        // GC records: one that matches the mirror's slot
+        typename F::GcRec g{};
+        g.slot = 5;
+        setkey(g, 10, 20, Z, W);
+        replay({g}, {});
+        expect(!tcp.kv.count(K) && T.n == 0 && T.tomb == 2 && T.host[5].w == CT_TOMBSTONE,
+               "gc match");
+        // one whose slot holds another key since, one whose slot is free,
+        // one a growth dropped (NONE): the map entry goes every time
+        const uint32_t WU = ct_word(17, 0, 0);
+        replay({}, {rec(7, 30, 40, Z, WU, CTI_CREATED, 0, 1), rec(8, 31, 41, Z, WU, CTI_CREATED, 0, 1),
+                    rec(9, 32, 42, Z, WU, CTI_CREATED, 0, 1)});
+        expect(any.kv.size() == 3 && T.n == 3 && T.tomb == 2, "gc setup");
+        g.slot = 7;
+        setkey(g, 31, 41, Z, WU);
+        replay({g}, {});
+        expect(any.kv.size() == 2 && !any.kv.count(mapkey(31, 41, Z, 17, 0)) && T.n == 3 &&
+                   T.tomb == 2 && T.host[7].w == CT_TOMBSTONE,
+               "gc other key");
+        g.slot = 12;
+        setkey(g, 32, 42, Z, WU);
+        replay({g}, {});
+        expect(any.kv.size() == 1 && T.n == 3 && T.tomb == 3 && T.host[12].w == CT_TOMBSTONE,
+               "gc free slot");
+        g.slot = 0xFFFFFFFFu;
+        setkey(g, 30, 40, Z, WU);
+        replay({g}, {});
+        expect(any.kv.empty() && T.n == 2 && T.tomb == 3, "gc dropped slot");
+        // the log out of (seq, order) order: the latest record's value stays
+        const std::string KL = mapkey(50, 60, 0, V6 ? 58 : 1, 0);
+        replay({}, {}, {logrec(50, 60, 2, 1, 333), logrec(50, 60, 2, 0, 222),
+                        logrec(50, 60, 1, 5, 111)});
+        v = tcp.kv.count(KL) ? &tcp.kv[KL].val : nullptr;
+        expect(v && tcp.kv.size() == 1 && at<uint32_t>(*v, 44) == 333 &&
+                   at<uint64_t>(*v, 0) == 1 && at<uint64_t>(*v, 8) == 84 &&
+                   at<uint32_t>(*v, 32) == 1060 && at<uint16_t>(*v, 36) == 16 &&
+                   at<uint32_t>(*v, 52) == 1000,
+               "log order");
+        // the lb_loopback bit: an IPv4 record carries it, an IPv6 one cannot
+        typename F::Log lo = logrec(51, 61, 3, 0, 1);
+        if constexpr (V6)
+            lo.rev = 9;
+        else
+            lo.lbw = 9 | 1u << 16;
+        lo.slave = 4;
+        replay({}, {}, {lo});
+        v = &tcp.kv[mapkey(51, 61, 0, V6 ? 58 : 1, 0)].val;
+        expect(v->size() == 56 && at<uint16_t>(*v, 36) == (V6 ? 16 : 16 | 8) &&
+                   at<uint16_t>(*v, 38) == 9 && at<uint16_t>(*v, 40) == 4,
+               "log loopback");
+        printf("ct_replay v%d %s\n", F::family, fail ? "FAIL" : "ok");
+        return fail;
+    }
+};
 
 // the cut rule of an egress batch with traffic to itself (selfcut.hpp)
 struct Row {
@@ -491,5 +695,7 @@ int main(int argc, char **argv)
     fail |= map_fuzz(gen);
     fail |= lpm4_tests(gen);
     fail |= hist_slot_tests(gen);
+    fail |= ReplayCase<false>().run();
+    fail |= ReplayCase<true>().run();
     return fail;
 }

@@ -1,7 +1,6 @@
 """Debug: the nat64_local_v6 stream as test_gpu_nat runs it (one batch),
 the engine's CT rows against the sequential oracle's; the rows only one
-side has, in hex, and the engine's stats.  CFC_CT_GROW_HOST=1 selects the
-host rebuild for growth (A/B)."""
+side has, in hex, and the engine's stats."""
 import os
 import sys
 

@@ -13,11 +13,13 @@ import numpy as np
 import pytest
 
 import oracle as O
+from cilium_amd import ctmap
 from cilium_amd import synth as S
 from cilium_amd import _lib as L
 from cilium_amd.datapath import Datapath
 from cilium_amd.loader import load_tables
 
+from test_gpu_ctgc import same_count, same_ct, step, step6
 from test_gpu_ctorder import check, run_both
 from test_gpu_parity import compare_with_oracle, run_gpu
 
@@ -81,3 +83,39 @@ def test_ct6_table_grows_inside_a_batch(torch):
     st = run_gpu.stats
     assert st["ct_grown"] >= 1 and st["ct_slots"] > before, (st, before)
     assert (st["ct_apply_device"], st["ct_apply_host"]) == (3, 0), st
+
+
+@pytest.mark.parametrize("family", [4, 6])
+def test_gc_log_survives_a_growth(torch, family):
+    """A GC's deletes the host has not taken yet, then a growth, then the
+    sync: ct_grow remaps the pending GC log's slots on the device, and a
+    plain tombstone the growth drops reads NONE when the log is replayed.
+    ~4k entries load into 8192 slots; batch A at 1000 leaves the oracle
+    3799 / 3877 entries; the GC at 1065 deletes 3147 / 3215 of them; batch B
+    at 1070 takes the oracle to 20941 / 26930 entries, far past 3/4 of the
+    slots, so its apply grows the table.  Nothing reads a CT map or syncs
+    between the load and the final dump, and no commit intervenes: the GC's
+    host-side deletes (the TCP maps' ICMP entries, which the device table
+    does not hold) are not journalled, so batch B finds nothing to commit
+    and no ct_sync runs before its growth."""
+    if family == 4:
+        t, flows = S.config_c5(5, n_flows=2_000, n_prefixes=20_000, n_policy=4000, now=1000)
+        headers, run, mode = S.headers_c5, step, 3
+    else:
+        t, flows = S.config_c5_v6(6, n_flows=2_000, n_prefixes=20_000, now=1000)
+        headers, run, mode = S.headers_c5_v6, step6, 0
+    t.ct_max_entries = 1 << 20
+    dp = Datapath(0)
+    load_tables(dp, t)
+    o = O.Oracle(t)
+    run(torch, dp, o, headers(t, flows, 20_000, seed=31, new_frac=0.1), 1000, mode)
+    f = ctmap.GCFilter(remove_expired=True)
+    ctmap.GC(dp, -1, f, now=1065)
+    st = dp.stats()
+    assert st["ct_grown"] == 0 and f.stats["device_deleted"] > 0, (st, f.stats)
+    same_count(f.stats, o.ct_gc(time=1065))
+    run(torch, dp, o, headers(t, flows, 200_000, seed=32, new_frac=0.5), 1070, mode)
+    st = dp.stats()
+    assert st["ct_grown"] >= 1 and st["ct_apply_host"] == 0, st
+    same_ct(dp, o)
+    dp.close()
