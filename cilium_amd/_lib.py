@@ -15,6 +15,7 @@ MODE_INGRESS, MODE_EGRESS, MODE_XDP, MODE_FULL = 0, 1, 2, 3
 HF_FRAG, HF_TCP_CLOSE, HF_EXTHDR = 0x100, 0x200, 0x400
 DROP_PREFILTER, VERDICT_PUNT = -1, -2
 OPT_LPM4, OPT_TIMING, OPT_CT_APPLY, OPT_CT_EVICT = 1, 2, 3, 4
+OPT_LPM4_DIR_BITS = 5
 CT_APPLY_DEVICE, CT_APPLY_HOST = 0, 1
 LPM4_AUTO, LPM4_DIR24_8, LPM4_TRIE = 0, 1, 2
 
@@ -33,7 +34,7 @@ EXPORTS = (
     "cfc_set_clock", "cfc_monitor_events_v4", "cfc_monitor_events_v6",
     "cfc_map_dump", "cfc_ct_gc",
     "cfc_proxy_entries_v4", "cfc_proxy_entries_v6",
-    "cfc_proxy_apply_v4", "cfc_proxy_apply_v6",
+    "cfc_proxy_apply_v4", "cfc_proxy_apply_v6", "cfc_lpm4_dir_stats",
 )
 # CT byte (cfc_out.ct): per stage (bits 0-3, then 4-7 for the destination's
 # ingress lookup after egress local delivery)
@@ -144,6 +145,12 @@ class ProxyStats(ctypes.Structure):
                 ("failed", ctypes.c_uint64)]
 
 
+class Lpm4DirStat(ctypes.Structure):
+    """cfc_lpm4_dir_stat (cfc_lpm4_dir_stats): one directory width"""
+    _fields_ = [("prefixes", ctypes.c_uint64), ("unresolved", ctypes.c_uint64),
+                ("bytes", ctypes.c_uint64)]
+
+
 class Timing(ctypes.Structure):
     _fields_ = [("launches", ctypes.c_uint64), ("classify_ms", ctypes.c_double),
                 ("count_ms", ctypes.c_double), ("launches_v6", ctypes.c_uint64),
@@ -207,6 +214,8 @@ def lib():
     L.cfc_identity_counters.argtypes = [vp, vp, u64, ctypes.POINTER(u64)]
     L.cfc_set_option.argtypes = [vp, i32, ctypes.c_int64]
     L.cfc_timing_collect.argtypes = [vp, ctypes.POINTER(Timing)]
+    if hasattr(L, "cfc_lpm4_dir_stats"):   # (a CFC_LIB build of an older tree has none)
+        L.cfc_lpm4_dir_stats.argtypes = [vp, ctypes.POINTER(Lpm4DirStat), pint]
     L.cfc_strerror.argtypes = [i32]
     L.cfc_strerror.restype = ctypes.c_char_p
     _lib = L

@@ -40,6 +40,7 @@ static int upload_vec(DevBuf &b, const std::vector<T> &v, hipStream_t s)
 struct GIpc {          // ipcache, IPv4
     DevBuf tbl24, tbl8, ovf, l4d, l4c, l4l;
     int layout = 0;
+    uint32_t l4_shift = 16;   // 32 - the directory's width (compact layout)
     uint32_t n_prefix4 = 0, tbl8_groups = 0, lpm4_kib = 0;
     uint64_t bytes = 0;
 };
@@ -321,6 +322,7 @@ void group_sigs(cfc_ctx *c, uint64_t sig[NGROUPS])
         sig[g] = 1469598103934665603ull + (uint64_t)g;
     auto mix = [&](int g, uint64_t v) { sig[g] = (sig[g] ^ v) * 1099511628211ull; };
     mix(0, (uint64_t)c->opts.lpm4);
+    mix(0, (uint64_t)c->opts.lpm4_dir_bits);
     mix(2, c->seclabel_gen);
     for (auto &kv : c->maps) {
         const Map *m = kv.second.get();
@@ -703,6 +705,8 @@ std::shared_ptr<GIpc> build_ipc(const HostImage &img, hipStream_t s, int *rc)
         (*rc = upload_vec(g->l4c, img.l4c, s)) || (*rc = upload_vec(g->l4l, img.l4l, s)))
         return nullptr;
     g->layout = img.lpm4_layout;
+    if (img.l4_dir_bits)
+        g->l4_shift = 32u - (uint32_t)img.l4_dir_bits;
     g->n_prefix4 = img.n_prefix4;
     g->tbl8_groups = (uint32_t)(img.tbl8.size() / 256);
     g->lpm4_kib = (uint32_t)((4ull * (img.l4d.size() + img.l4c.size() + img.tbl24.size() +
@@ -902,6 +906,7 @@ void assemble(Epoch &E)
     const GCt &C = *E.ct;
     const GLb &B = *E.lb;
     T.l4d = (const uint4 *)I.l4d.p;
+    T.l4_shift = I.l4_shift;
     T.l4c = (const uint32_t *)I.l4c.p;
     T.l4l = (const uint64_t *)I.l4l.p;
     T.tbl24 = (const uint32_t *)I.tbl24.p;
@@ -1488,6 +1493,11 @@ int cfc_set_option(cfc_ctx *c, int option, int64_t value)
             return -EINVAL;
         c->opts.lpm4 = (int)value;   // the next commit rebuilds (tables_sig)
         return 0;
+    case CFC_OPT_LPM4_DIR_BITS:
+        if (value != 0 && (value < L4_DIR_BITS_MIN || value > L4_DIR_BITS_MAX))
+            return -EINVAL;
+        c->opts.lpm4_dir_bits = (int)value;   // the next commit rebuilds
+        return 0;
     case CFC_OPT_TIMING:
         if (value != 0 && value != 1)
             return -EINVAL;
@@ -1508,6 +1518,32 @@ int cfc_set_option(cfc_ctx *c, int option, int64_t value)
     default:
         return -EINVAL;
     }
+}
+
+int cfc_lpm4_dir_stats(cfc_ctx *c, cfc_lpm4_dir_stat st[3], int *auto_bits)
+{
+    if (!c || !st)
+        return -EINVAL;
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    std::vector<Pfx4> pfx;
+    std::vector<uint32_t> ovf, d, ch;
+    std::vector<uint64_t> l;
+    for (auto &kv : c->maps)
+        if (kv.second->role == ROLE_IPCACHE)
+            ipcache_v4_prefixes(kv.second.get(), &pfx, &ovf);
+    int a = l4_auto_dir_bits(pfx);
+    for (int i = 2; i >= 0; i--) {
+        const int D = L4_DIR_BITS_MIN + i;
+        st[i].prefixes = pfx.size();
+        st[i].unresolved = l4_unresolved(pfx, D);
+        build_l4trie(pfx, &ovf, &d, &ch, &l, D);
+        st[i].bytes = 4ull * (d.size() + ch.size()) + 8ull * l.size();
+        if (a == D && D > L4_DIR_BITS_MIN && st[i].bytes > L4_AUTO_BUDGET)
+            a--;   // (as build_image narrows)
+    }
+    if (auto_bits)
+        *auto_bits = a;
+    return 0;
 }
 
 int cfc_timing_collect(cfc_ctx *c, cfc_timing *out)

@@ -124,7 +124,7 @@ __device__ __forceinline__ uint32_t mkey(int reason, int dir)
 struct Hdr {
     uint32_t sa, da, pt, mt, mk;
     bool valid;
-    uint4 l4d;                   // the /16 directory entry (compact LPM)
+    uint4 l4d;                   // the directory entry (compact LPM)
     uint32_t e24, pfd, lh, hsh, lxs, lss, pfb;
     uint4 lx, ls, pf, rec;
     bool pf_maybe;
@@ -235,7 +235,7 @@ __device__ __forceinline__ void r2_issue(const DevTables &T, const Lds &S,
 #if CFC_EXP == 1
             h.l4d = make_uint4(h.lh & 0xFFFF, 0, 0, 0);
 #else
-            h.l4d = ldt16(T.l4d, (h.lh >> 16) * 16u);
+            h.l4d = ldt16(T.l4d, (h.lh >> T.l4_shift) * 16u);
 #endif
         else if (T.tbl24)
             h.e24 = T.tbl24[h.lh >> 8];
@@ -686,14 +686,17 @@ __device__ __forceinline__ void acc_publish(const unsigned long long *s_met,
 // no prefilter LPM, the endpoint table and both Bloom filters in LDS, and
 // (modes with XDP) a prefilter /32 set.  The tests of that shape and the
 // pointers of the other layouts are then compile-time facts, which frees the
-// SGPRs and exec-mask pairs they would hold for the whole loop.
-template <int MODE, int U, bool CT, bool NT, bool OPT, bool LB, bool FAST>
+// SGPRs and exec-mask pairs they would hold for the whole loop.  FAST is the
+// width of the LPM directory (16, 17 or 18, layout.h; 0: the generic
+// kernel), so its shift is a constant too and costs no SGPR.
+template <int MODE, int U, bool CT, bool NT, bool OPT, bool LB, int FAST>
 __global__ __launch_bounds__(BLOCK, WAVES_PER_SIMD) void k_classify_v4(
     DevTables T, LdsPlan L, cfc_hdr_v4 in, cfc_out out, EgressArgs E,
     CountArgs C, uint64_t per_block, LbIn LI)
 {
     if (FAST) {
         T.tbl24 = T.tbl8 = T.pf_tbl24 = T.pf_tbl8 = nullptr;
+        T.l4_shift = 32 - FAST;
         __builtin_assume(T.l4d != nullptr);
         __builtin_assume(T.lxc4 != nullptr);
         if (MODE == CFC_MODE_XDP || MODE == CFC_MODE_FULL)
@@ -1773,7 +1776,7 @@ __global__ __launch_bounds__(256) void k_patch16(const Patch16 *rec, uint64_t n)
 #ifndef CFC_FAST
 #define CFC_FAST 1   // 0: always the generic kernel (A/B builds)
 #endif
-// the epoch shape k_classify_v4<..., FAST = true> is compiled for
+// the epoch shape k_classify_v4<..., FAST != 0> is compiled for
 bool fast_shape(const DevTables &T, int mode, const LdsPlan &L)
 {
     if (!CFC_FAST)
@@ -1790,15 +1793,22 @@ void launch_mode_nt(const DevTables &T, const cfc_hdr_v4 &in, const cfc_out &out
 {
     const LdsPlan L = lds_plan(T);
     const bool opt = in.mark || in.tcp_flags || out.action || (CT && out.ct);
-    const bool fast = fast_shape(T, MODE, L);
-    auto kern = opt ? (fast ? k_classify_v4<MODE, CFC_UNROLL, CT, NT, true, false, true>
-                            : k_classify_v4<MODE, CFC_UNROLL, CT, NT, true, false, false>)
-                    : (fast ? k_classify_v4<MODE, CFC_UNROLL, CT, NT, false, false, true>
-                            : k_classify_v4<MODE, CFC_UNROLL, CT, NT, false, false, false>);
+    const int fast = fast_shape(T, MODE, L) ? 32 - (int)T.l4_shift : 0;
+    auto kern = opt ? k_classify_v4<MODE, CFC_UNROLL, CT, NT, true, false, 0>
+                    : k_classify_v4<MODE, CFC_UNROLL, CT, NT, false, false, 0>;
+    if (fast == 16)
+        kern = opt ? k_classify_v4<MODE, CFC_UNROLL, CT, NT, true, false, 16>
+                   : k_classify_v4<MODE, CFC_UNROLL, CT, NT, false, false, 16>;
+    else if (fast == 17)
+        kern = opt ? k_classify_v4<MODE, CFC_UNROLL, CT, NT, true, false, 17>
+                   : k_classify_v4<MODE, CFC_UNROLL, CT, NT, false, false, 17>;
+    else if (fast == 18)
+        kern = opt ? k_classify_v4<MODE, CFC_UNROLL, CT, NT, true, false, 18>
+                   : k_classify_v4<MODE, CFC_UNROLL, CT, NT, false, false, 18>;
     const LbIn none{};
     if constexpr (CT && MODE != CFC_MODE_XDP) {
         if (lb)
-            kern = k_classify_v4<MODE, CFC_UNROLL, CT, NT, true, true, false>;
+            kern = k_classify_v4<MODE, CFC_UNROLL, CT, NT, true, true, 0>;
     }
     set_lds_limit((const void *)kern, (int)LDS_PER_WG);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), L.bytes(), s, T, L, in,

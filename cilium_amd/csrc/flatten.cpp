@@ -66,6 +66,7 @@ namespace {
 struct L4Trie {
     std::vector<uint32_t> *d, *c, *ovf;
     std::vector<uint64_t> *l;
+    int dbits;
     bool ok = true;
 
     // list-entry leaf: 26 payload bits, wider labels through lbl_ovf
@@ -86,7 +87,8 @@ struct L4Trie {
 
     // The node for the range `base`/`lvl` whose own covering leaf is `def`;
     // `longp` holds the prefixes longer than lvl inside the range.  At the
-    // /16 level (dir != null) the longest two go into the directory entry.
+    // directory level (dir != null) the longest two go into the directory
+    // entry.
     uint32_t node(std::vector<Pfx4> &longp, uint32_t base, int lvl, uint32_t def,
                   uint32_t *dir = nullptr)
     {
@@ -100,7 +102,7 @@ struct L4Trie {
                 uint64_t e[L4_INLINE] = {0, 0};
                 for (; first < longp.size() && first < L4_INLINE; first++)
                     e[first] = l4_inline_entry(longp[first].addr, longp[first].plen,
-                                               list_leaf(longp[first].leaf));
+                                               list_leaf(longp[first].leaf), 32 - dbits);
                 dir[1] = (uint32_t)e[0];
                 dir[2] = (uint32_t)(e[0] >> 32) | (uint32_t)(e[1] << 16);
                 dir[3] = (uint32_t)(e[1] >> 16);
@@ -117,18 +119,19 @@ struct L4Trie {
                 ok = false;
             return L4_PTR | (uint32_t)(l->size() - off) << 24 | (uint32_t)(off & L4_OFF);
         }
-        // split: a chunk for the next 8 bits
-        const int nl = lvl + 8;
+        // split: a chunk for the next min(8, 32 - lvl) bits
+        const uint32_t bits = l4_chunk_bits(32 - lvl), n = 1u << bits;
+        const int nl = lvl + (int)bits;
         const uint32_t sh = 32 - nl;
         const size_t off = c->size();
-        c->resize(off + 256, 0);
+        c->resize(off + n, 0);
         uint32_t defs[256];
-        std::fill(defs, defs + 256, def);
-        std::vector<std::vector<Pfx4>> sub(256);
+        std::fill(defs, defs + n, def);
+        std::vector<std::vector<Pfx4>> sub(n);
         std::stable_sort(longp.begin(), longp.end(),
                          [](const Pfx4 &a, const Pfx4 &b) { return a.plen < b.plen; });
         for (const Pfx4 &p : longp) {
-            const uint32_t j = (p.addr >> sh) & 255;
+            const uint32_t j = (p.addr >> sh) & (n - 1);
             if (p.plen <= nl) {
                 const uint32_t span = 1u << (nl - p.plen);
                 std::fill(defs + (j & ~(span - 1)), defs + (j & ~(span - 1)) + span, p.leaf);
@@ -136,7 +139,7 @@ struct L4Trie {
                 sub[j].push_back(p);
             }
         }
-        for (uint32_t j = 0; j < 256; j++) {
+        for (uint32_t j = 0; j < n; j++) {
             const uint32_t e = node(sub[j], base | (j << sh), nl, defs[j]);
             (*c)[off + j] = e;
         }
@@ -150,31 +153,61 @@ struct L4Trie {
 
 bool build_l4trie(std::vector<Pfx4> pfx, std::vector<uint32_t> *ovf,
                   std::vector<uint32_t> *l4d, std::vector<uint32_t> *l4c,
-                  std::vector<uint64_t> *l4l)
+                  std::vector<uint64_t> *l4l, int dir_bits)
 {
+    const int D = dir_bits;
     std::stable_sort(pfx.begin(), pfx.end(),
                      [](const Pfx4 &a, const Pfx4 &b) { return a.plen < b.plen; });
-    l4d->assign(4u << 16, 0);
+    l4d->assign((size_t)4 << D, 0);
     l4c->clear();
     l4l->clear();
-    // /0../16: paint the directory's covering leaves, shortest first
+    // /0../D: paint the directory's covering leaves, shortest first
     for (const Pfx4 &p : pfx) {
-        if (p.plen > 16)
+        if (p.plen > D)
             break;
-        const uint32_t start = p.plen ? (p.addr >> 16) & ~((1u << (16 - p.plen)) - 1) : 0;
-        for (uint32_t j = start; j < start + (1u << (16 - p.plen)); j++)
-            (*l4d)[4 * j] = p.leaf;
+        const uint32_t start = p.plen ? (p.addr >> (32 - D)) & ~((1u << (D - p.plen)) - 1) : 0;
+        for (uint32_t j = start; j < start + (1u << (D - p.plen)); j++)
+            (*l4d)[4 * (size_t)j] = p.leaf;
     }
-    std::map<uint32_t, std::vector<Pfx4>> by16;
+    std::map<uint32_t, std::vector<Pfx4>> byd;
     for (const Pfx4 &p : pfx)
-        if (p.plen > 16)
-            by16[p.addr >> 16].push_back(p);
-    L4Trie b{l4d, l4c, ovf, l4l};
-    for (auto &g : by16) {
-        uint32_t *dir = l4d->data() + 4 * g.first;
-        dir[0] = b.node(g.second, g.first << 16, 16, dir[0], dir);
+        if (p.plen > D)
+            byd[p.addr >> (32 - D)].push_back(p);
+    L4Trie b{l4d, l4c, ovf, l4l, D};
+    for (auto &g : byd) {
+        uint32_t *dir = l4d->data() + 4 * (size_t)g.first;
+        dir[0] = b.node(g.second, g.first << (32 - D), D, dir[0], dir);
     }
     return b.ok;
+}
+
+// what a directory of `dir_bits` bits leaves to a second load: over its
+// entries, the prefixes longer than the directory beyond the two inline
+uint64_t l4_unresolved(const std::vector<Pfx4> &pfx, int dir_bits)
+{
+    std::vector<uint32_t> idx;
+    for (const Pfx4 &p : pfx)
+        if (p.plen > dir_bits)
+            idx.push_back(p.addr >> (32 - dir_bits));
+    std::sort(idx.begin(), idx.end());
+    uint64_t un = 0;
+    for (size_t i = 0, j; i < idx.size(); i = j) {
+        for (j = i; j < idx.size() && idx[j] == idx[i];)
+            j++;
+        un += j - i > L4_INLINE ? j - i - L4_INLINE : 0;
+    }
+    return un;
+}
+
+int l4_auto_dir_bits(const std::vector<Pfx4> &pfx)
+{
+    int D = L4_DIR_BITS_MIN;
+    // (a directory that is over the budget on its own is not tried)
+    for (; D < L4_DIR_BITS_MAX && (32ull << D) <= L4_AUTO_BUDGET; D++)
+        if (l4_unresolved(pfx, D) * L4_AUTO_SHARE_DEN < pfx.size() * L4_AUTO_SHARE_NUM ||
+            pfx.empty())
+            break;
+    return D;
 }
 
 // ---- IPv6 LPM (layout.h Lpm6)
@@ -375,6 +408,11 @@ static void ipcache_v4(const Map *m, std::vector<Pfx4> *out,
     for (const auto &b : best)
         out->push_back({b.first.first, (uint8_t)b.first.second,
                         leaf_for(b.second.second, ovf)});
+}
+
+void ipcache_v4_prefixes(const Map *m, std::vector<Pfx4> *out, std::vector<uint32_t> *ovf)
+{
+    ipcache_v4(m, out, ovf);
 }
 
 // Effective IPv6 prefixes of the ipcache: as ipcache_v4 with the v6 lookup
@@ -816,15 +854,28 @@ void build_image(const std::vector<Map *> &maps, const BuildOpts &opt,
         if (!pfx.empty()) {
             const size_t n_ovf = img->lbl_ovf.size();
             bool trie = opt.lpm4 != LPM4_DIR24_8;
-            if (trie && !build_l4trie(pfx, &img->lbl_ovf, &img->l4d, &img->l4c,
-                                      &img->l4l)) {
+            for (int D = 0; D < 3; D++)
+                img->l4_unresolved[D] = l4_unresolved(pfx, L4_DIR_BITS_MIN + D);
+            // the directory width: forced, or (auto) the narrowest that
+            // leaves few enough prefixes to a second load, narrowed again
+            // while the layout is over its L2 budget
+            int D = opt.lpm4_dir_bits ? opt.lpm4_dir_bits : l4_auto_dir_bits(pfx);
+            for (; trie; D--) {
+                img->lbl_ovf.resize(n_ovf);
+                trie = build_l4trie(pfx, &img->lbl_ovf, &img->l4d, &img->l4c, &img->l4l, D);
+                const uint64_t bytes = 4ull * (img->l4d.size() + img->l4c.size()) +
+                                       8ull * img->l4l.size();
+                if (opt.lpm4_dir_bits || D == L4_DIR_BITS_MIN || bytes <= L4_AUTO_BUDGET)
+                    break;
+            }
+            if (!trie) {
                 img->l4d.clear();
                 img->l4c.clear();
                 img->l4l.clear();
                 img->lbl_ovf.resize(n_ovf);
-                trie = false;
             }
             if (trie) {
+                img->l4_dir_bits = D;
                 img->lpm4_layout = LPM4_TRIE;
             } else {
                 build_dir24_8(pfx, &img->tbl24, &img->tbl8);

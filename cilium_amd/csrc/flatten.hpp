@@ -19,8 +19,22 @@ struct PolLoc {
 // IPv4 ipcache layouts (cfc_set_option CFC_OPT_LPM4)
 enum Lpm4Layout { LPM4_AUTO = 0, LPM4_DIR24_8 = 1, LPM4_TRIE = 2 };
 
+// The compact layout's directory width (cfc_set_option
+// CFC_OPT_LPM4_DIR_BITS; layout.h l4d).  Auto takes the narrowest width that
+// leaves less than L4_AUTO_SHARE_NUM / L4_AUTO_SHARE_DEN of the prefixes to a
+// second load (l4_unresolved), else the widest, as long as l4d + l4c + l4l
+// stay within L4_AUTO_BUDGET bytes (it narrows again while they do not).
+// Both constants come from the C2 measurements in DESIGN.md section 4
+// "Directory width": 19 % of the C2 prefixes unresolved at /16 cost 5 % of
+// the classify kernel, 7 % at /17 and 2 % at /18 measure the same, and a
+// 4 MiB directory fills an XCD's L2 on its own.
+constexpr int L4_DIR_BITS_MIN = 16, L4_DIR_BITS_MAX = 18;
+constexpr uint64_t L4_AUTO_SHARE_NUM = 1, L4_AUTO_SHARE_DEN = 10;
+constexpr uint64_t L4_AUTO_BUDGET = 3u << 20;
+
 struct BuildOpts {
     int lpm4 = LPM4_AUTO;
+    int lpm4_dir_bits = 0;   // 0 = auto, or 16..18
 };
 
 // IPv6 LPM (layout.h Lpm6), host side
@@ -61,8 +75,11 @@ struct HostImage {
     uint64_t ct_min4 = 0, ct_min6 = 0;
     // IPv4 ipcache: compact multibit (l4c/l4l) or DIR-24-8 (tbl24/tbl8)
     std::vector<uint32_t> tbl24, tbl8, lbl_ovf;
-    std::vector<uint32_t> l4d, l4c;    // l4d: 4 words per /16
+    std::vector<uint32_t> l4d, l4c;    // l4d: 4 words per directory entry
     std::vector<uint64_t> l4l;
+    int l4_dir_bits = 0;           // the directory's width (compact layout)
+    // per width 16, 17, 18: prefixes its directory load cannot resolve
+    uint64_t l4_unresolved[3] = {0, 0, 0};
     int lpm4_layout = 0;           // LPM4_DIR24_8 / LPM4_TRIE, 0 = empty
     uint32_t n_prefix4 = 0;
     // prefilter
@@ -147,6 +164,14 @@ void build_dir24_8(std::vector<Pfx4> pfx, std::vector<uint32_t> *tbl24,
 // lbl_ovf entries.  False when an offset would not fit its 24 bits.
 bool build_l4trie(std::vector<Pfx4> pfx, std::vector<uint32_t> *ovf,
                   std::vector<uint32_t> *l4d, std::vector<uint32_t> *l4c,
-                  std::vector<uint64_t> *l4l);
+                  std::vector<uint64_t> *l4l, int dir_bits = L4_DIR_BITS_MIN);
+// the prefixes a directory of dir_bits bits cannot resolve in its one load:
+// over its entries, max(0, prefixes longer than dir_bits - L4_INLINE)
+uint64_t l4_unresolved(const std::vector<Pfx4> &pfx, int dir_bits);
+// the width auto starts from (before the byte budget, build_image)
+int l4_auto_dir_bits(const std::vector<Pfx4> &pfx);
+// the IPv4 prefixes of an ipcache map as the LPM builders take them (ovf:
+// labels too wide for a leaf)
+void ipcache_v4_prefixes(const Map *m, std::vector<Pfx4> *out, std::vector<uint32_t> *ovf);
 
 }  // namespace cfc

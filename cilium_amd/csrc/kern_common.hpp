@@ -160,7 +160,7 @@ __device__ __forceinline__ uint32_t lds_word(uint32_t off)
     return reinterpret_cast<const uint32_t *>(cfc_smem)[off];
 }
 
-// ---- compact IPv4 LPM (layout.h): walk from the /16 directory word `e`
+// ---- compact IPv4 LPM (layout.h): walk from the directory word `e`
 // through chunks to a leaf or a prefix list; the first list entry that
 // matches is the longest prefix.  Returns the label (0 = no match).
 __device__ __forceinline__ uint32_t l4_leaf(const DevTables &T, uint32_t e)
@@ -177,17 +177,18 @@ __device__ __forceinline__ uint32_t l4_lookup(const DevTables &T, uint32_t a,
 {
     // the directory's inline prefixes first (longest first, layout.h)
     const uint32_t e1 = (d.z >> 16) | (d.w << 16);
-    if (l4_inline_match(a, d.y))
+    uint32_t shift = T.l4_shift;   // address bits below the current node
+    if (l4_inline_match(a, d.y, shift))
         return l4_list_leaf(T, (d.y >> 21) | (d.z << 11));
-    if (l4_inline_match(a, e1))
+    if (l4_inline_match(a, e1, shift))
         return l4_list_leaf(T, d.w >> 5);
     uint32_t e = d.x;
-    uint32_t shift = 16;   // address bits below the current node
     while (e & L4_PTR) {
         const uint32_t cnt = (e >> 24) & 127, off = e & L4_OFF;
         if (cnt == 0) {
-            shift -= 8;
-            e = T.l4c[off + ((a >> shift) & 255)];
+            const uint32_t bits = l4_chunk_bits(shift);
+            shift -= bits;
+            e = T.l4c[off + ((a >> shift) & ((1u << bits) - 1))];
             continue;
         }
         for (uint32_t i = 0; i < cnt; i += 2) {

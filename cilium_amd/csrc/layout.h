@@ -45,15 +45,19 @@ constexpr uint32_t EMPTY = 0xFFFFFFFFu;
 // DIR-24-8 costs ~1.3 Infinity-Cache accesses per lookup (tbl24 is 64 MiB).
 // The compact layout keeps the whole ipcache in about 2-3 MiB, resident in
 // every XCD's 4 MiB L2, and resolves most lookups with ONE 16-byte load:
-//   l4d (16 B x 65536) the /16 directory.  x = the node word (below); y, z, w
-//                    hold up to two of the node's prefixes longer than /16
+//   l4d (16 B x 2^D) the /D directory, D = dir_bits of the epoch: 16, 17 or 18
+//                    (DevTables.l4_shift = 32 - D; flatten.cpp picks D from
+//                    the table).  x = the node word (below); y, z, w
+//                    hold up to two of the node's prefixes longer than /D
 //                    inline (48-bit entries, below), its longest two, which
-//                    a lookup checks before following x: a /16 with at most
+//                    a lookup checks before following x: a /D with at most
 //                    two longer prefixes is a single load (x is then the
 //                    covering leaf), a longer list continues in l4l
-//   l4c (u32 nodes)  256-entry chunks for the next 8 bits.  A node word is
+//   l4c (u32 nodes)  chunks for the next min(8, 32 - level) bits: levels
+//                    16-24-32, 17-25-32 (the last chunk has 128 entries) or
+//                    18-26-32 (64 entries).  A node word is
 //      bit31 clear              a leaf (LPM leaf encoding above; 0 = none)
-//      bit31 set, cnt == 0      a chunk at l4c[off] for the next 8 bits
+//      bit31 set, cnt == 0      a chunk at l4c[off] for the next bits
 //      bit31 set, cnt  > 0      a list of cnt prefixes at l4l[off]
 //                    (off = bits 0-23, cnt = bits 24-30)
 //   l4l (u64)        per-node prefix lists, longest first, ending with the
@@ -62,10 +66,11 @@ constexpr uint32_t EMPTY = 0xFFFFFFFFu;
 //                    lo = prefix address (host order, masked),
 //                    hi = (len & 31) << 27 | leaf27 (LL_INDIRECT -> lbl_ovf)
 // A node lists its prefixes while it has fewer than L4_LIST_MAX, and is
-// split into a chunk beyond (a split /16 has no inline entries).
+// split into a chunk beyond (a split /D has no inline entries).
 // Inline entry (48 bits; e0 = y | (z & 0xFFFF) << 32, e1 = z >> 16 | w << 16):
-//   bits 0-15 the prefix's address bits 0-15 (masked), bits 16-20 len - 16
-//   (1..16: never 0, so a zero entry is empty), bits 21-47 leaf27.
+//   bits 0-15 the prefix's address bits below the directory index (32 - D of
+//   them, masked), bits 16-20 len - D (1..32 - D: never 0, so a zero entry is
+//   empty), bits 21-47 leaf27.
 constexpr uint32_t L4_PTR = 0x80000000u;
 constexpr uint32_t L4_OFF = 0xFFFFFFu;
 constexpr uint32_t L4_LIST_MAX = 16;
@@ -78,19 +83,26 @@ __host__ __device__ inline bool l4_match(uint32_t a, uint32_t addr, uint32_t hi)
     const uint32_t m = len ? 0xFFFFFFFFu << (32 - len) : 0xFFFFFFFFu;
     return (a & m) == addr;
 }
+// `shift` = 32 - dir_bits: the address bits below the directory index
 __host__ __device__ inline uint64_t l4_inline_entry(uint32_t addr, uint32_t len,
-                                                    uint32_t leaf27)
+                                                    uint32_t leaf27, uint32_t shift)
 {
-    return (uint64_t)(addr & 0xFFFFu) | (uint64_t)(len - 16) << 16 |
-           (uint64_t)leaf27 << 21;
+    return (uint64_t)(addr & ~(0xFFFFFFFFu << shift)) |
+           (uint64_t)(len - (32 - shift)) << 16 | (uint64_t)leaf27 << 21;
 }
 // does inline entry e (nonzero) hold a prefix containing address a (whose
-// top 16 bits are the directory index)
-__host__ __device__ inline bool l4_inline_match(uint32_t a, uint32_t e_lo32)
+// top dir_bits bits are the directory index)
+__host__ __device__ inline bool l4_inline_match(uint32_t a, uint32_t e_lo32, uint32_t shift)
 {
-    const uint32_t l = (e_lo32 >> 16) & 31;            // len - 16, 0 = empty
-    const uint32_t m = (0xFFFFu << (16 - l)) & 0xFFFFu;
+    const uint32_t l = (e_lo32 >> 16) & 31;            // len - dir_bits, 0 = empty
+    const uint32_t m = (0xFFFFFFFFu << (shift - l)) & ~(0xFFFFFFFFu << shift);
     return l != 0 && ((a ^ e_lo32) & m) == 0;
+}
+// a chunk below a node with `shift` address bits under it takes the next
+// min(8, shift) bits
+__host__ __device__ inline uint32_t l4_chunk_bits(uint32_t shift)
+{
+    return shift < 8 ? shift : 8;
 }
 
 // ---- policy: open addressing, linear probing over 16-byte slots -------------
@@ -413,7 +425,7 @@ __host__ __device__ inline uint32_t lb6_hash(uint32_t a0, uint32_t a1, uint32_t 
 }
 
 struct DevTables {
-    const uint4 *l4d;              // compact IPv4 LPM /16 directory, or null
+    const uint4 *l4d;              // compact IPv4 LPM directory, or null
     const uint32_t *l4c;           // its chunks
     const uint64_t *l4l;           // its prefix lists
     const uint32_t *tbl24;         // DIR-24-8 layout (null: none or compact)
@@ -433,6 +445,7 @@ struct DevTables {
     uint32_t pf_bloom_words;       // power of two, 0 = no filter
     uint32_t pol_bloom_words;      // power of two, 0 = no filter
     uint32_t lxc4_lds;             // 1: the endpoint table is copied to LDS
+    uint32_t l4_shift;             // 32 - dir_bits of l4d (16, 15 or 14)
     // IPv6
     Lpm6 ipc6;                     // ipcache
     Lpm6 pf6_fix;                  // prefilter exact /128 set (one length)

@@ -358,24 +358,26 @@ static uint32_t dir24_lookup_host(const std::vector<uint32_t> &t24,
 }
 static uint32_t l4_lookup_host(const std::vector<uint32_t> &d, const std::vector<uint32_t> &c,
                                const std::vector<uint64_t> &l, const std::vector<uint32_t> &ovf,
-                               uint32_t a)
+                               uint32_t a, int dir_bits)
 {
     auto list_leaf = [&](uint32_t hi) {
         const uint32_t x = hi & (LL_INDIRECT | LL_PAYLOAD);
         return (x & LL_INDIRECT) ? ovf[x & LL_PAYLOAD] : x;
     };
-    const uint32_t *D = &d[4 * (a >> 16)];
+    uint32_t shift = 32u - (uint32_t)dir_bits;
+    const uint32_t *D = &d[4 * (size_t)(a >> shift)];
     const uint32_t e1 = (D[2] >> 16) | (D[3] << 16);
-    if (l4_inline_match(a, D[1]))
+    if (l4_inline_match(a, D[1], shift))
         return list_leaf((D[1] >> 21) | (D[2] << 11));
-    if (l4_inline_match(a, e1))
+    if (l4_inline_match(a, e1, shift))
         return list_leaf(D[3] >> 5);
-    uint32_t e = D[0], shift = 16;
+    uint32_t e = D[0];
     while (e & L4_PTR) {
         const uint32_t cnt = (e >> 24) & 127, off = e & L4_OFF;
         if (cnt == 0) {
-            shift -= 8;
-            e = c[off + ((a >> shift) & 255)];
+            const uint32_t bits = l4_chunk_bits(shift);
+            shift -= bits;
+            e = c.at(off + ((a >> shift) & ((1u << bits) - 1)));
             continue;
         }
         for (uint32_t i = 0; i < cnt; i += 2) {
@@ -388,7 +390,10 @@ static uint32_t l4_lookup_host(const std::vector<uint32_t> &d, const std::vector
     }
     return (e & LPM_INDIRECT) ? ovf[e & LPM_PAYLOAD] : e;
 }
-static int lpm4_case(const char *name, std::vector<Pfx4> pfx, std::mt19937 &gen, int nq)
+// (probes: addresses every case asks besides the random ones; one line per
+// directory width, and a line for the case unless it has probes)
+static int lpm4_case(const char *name, std::vector<Pfx4> pfx, std::mt19937 &gen, int nq,
+                     const std::vector<uint32_t> &probes = {})
 {
     {   // one prefix per (masked address, length), as the ipcache map holds
         std::map<std::pair<uint32_t, int>, Pfx4> u;
@@ -400,14 +405,18 @@ static int lpm4_case(const char *name, std::vector<Pfx4> pfx, std::mt19937 &gen,
         for (auto &kv : u)
             pfx.push_back(kv.second);
     }
-    std::vector<uint32_t> t24, t8, ovf, d, c;
-    std::vector<uint64_t> l;
+    std::vector<uint32_t> t24, t8, ovf[3], d[3], c[3];
+    std::vector<uint64_t> l[3];
     build_dir24_8(pfx, &t24, &t8);
-    const bool ok = build_l4trie(pfx, &ovf, &d, &c, &l);
-    int bad = !ok;
-    for (int q = 0; q < nq; q++) {
+    int bad = 0;
+    for (int D = 16; D <= 18; D++)
+        bad += !build_l4trie(pfx, &ovf[D - 16], &d[D - 16], &c[D - 16], &l[D - 16], D) ||
+               d[D - 16].size() != (size_t)4 << D;
+    for (int q = 0; q < nq + (int)probes.size(); q++) {
         uint32_t a = gen();
-        if (!pfx.empty() && (q & 3)) {   // mostly inside some prefix
+        if (q >= nq) {
+            a = probes[q - nq];
+        } else if (!pfx.empty() && (q & 3)) {   // mostly inside some prefix
             const Pfx4 &p = pfx[gen() % pfx.size()];
             const uint32_t m = p.plen ? 0xFFFFFFFFu << (32 - p.plen) : 0u;
             a = p.addr | (a & ~m);
@@ -419,12 +428,22 @@ static int lpm4_case(const char *name, std::vector<Pfx4> pfx, std::mt19937 &gen,
             if ((int)p.plen > best && (a & m) == p.addr)
                 best = p.plen, want = p.leaf;
         }
-        const uint32_t x = dir24_lookup_host(t24, t8, a), y = l4_lookup_host(d, c, l, ovf, a);
-        if ((x != want || y != want) && bad++ < 5)
-            printf("%s: %08x -> dir24 %u, trie %u, want %u\n", name, a, x, y, want);
+        const uint32_t x = dir24_lookup_host(t24, t8, a);
+        if (x != want && bad++ < 5)
+            printf("%s: %08x -> dir24 %u, want %u\n", name, a, x, want);
+        for (int D = 16; D <= 18; D++) {
+            const uint32_t y =
+                l4_lookup_host(d[D - 16], c[D - 16], l[D - 16], ovf[D - 16], a, D);
+            if (y != want && bad++ < 5)
+                printf("%s: %08x -> trie /%d %u, want %u\n", name, a, D, y, want);
+        }
     }
-    printf("lpm4 %-14s prefixes %5zu chunks %5zu list %6zu: %s\n", name, pfx.size(),
-           c.size() / 256, l.size(), bad ? "FAIL" : "ok");
+    for (int D = 16; D <= 18; D++)
+        printf("lpm4 %-14s /%d chunk words %6zu list %6zu unresolved %5llu -> %s\n", name, D,
+               c[D - 16].size(), l[D - 16].size(), (unsigned long long)l4_unresolved(pfx, D),
+               bad ? "FAIL" : "ok");
+    if (probes.empty())
+        printf("lpm4 %-14s prefixes %5zu: %s\n", name, pfx.size(), bad ? "FAIL" : "ok");
     return bad != 0;
 }
 static int lpm4_tests(std::mt19937 &gen)
@@ -458,6 +477,64 @@ static int lpm4_tests(std::mt19937 &gen)
         char nm[32];
         snprintf(nm, sizeof nm, "small-%d", n);
         fail |= lpm4_case(nm, v, gen, 5000);
+    }
+    // the edges of a /D directory, one table per D (every table is looked up
+    // at all three widths)
+    for (int D = 16; D <= 18; D++) {
+        v.clear();
+        std::vector<uint32_t> pr;
+        const uint32_t sh = 32 - D, wide = 1u << 26;
+        // lengths D-1, D, D+1 and 32 at one address: the painting over two
+        // entries, the entry's own leaf, a len - D = 1 inline entry
+        const uint32_t A = 0x0A140000u;
+        v.push_back({A, (uint8_t)(D - 1), 11});
+        v.push_back({A, (uint8_t)D, 12});
+        v.push_back({A, (uint8_t)(D + 1), 13});
+        v.push_back({A + 1, 32, 14});
+        for (uint32_t o : {0u, 1u, 2u, 1u << (sh - 1), (1u << (sh - 1)) - 1, 1u << sh,
+                           (1u << sh) - 1, 2u << sh, (2u << sh) - 1, ~0u})
+            pr.push_back(A + o);
+        // a /D node with 2 (inline only), 3 (the shortest list), 14 (the
+        // longest) and 15 (split) longer prefixes; a label past 26 bits on
+        // the longest (inline) and on the shortest (list, or a chunk leaf)
+        uint32_t k = 0;
+        for (int n : {2, 3, 14, 15}) {
+            const uint32_t N = 0x0A200000u + (k++ << sh);
+            for (int i = 0; i < n; i++) {
+                const uint32_t a = N | (uint32_t)(i + 1) << 4;
+                const uint8_t len = i == 0 ? 32 : i == n - 1 ? D + 1 : 28;
+                const uint32_t m = 0xFFFFFFFFu << (32 - len);
+                v.push_back({a & m, len,
+                             i == 0 || i == n - 1 ? wide + 100u * n + i : 100u * n + i});
+                for (uint32_t o : {0u, 1u, 15u, 16u})
+                    pr.push_back(a + o);
+            }
+            pr.push_back(N);
+            pr.push_back(N + (1u << sh) - 1);
+            pr.push_back(N + (1u << (sh - 1)));
+            pr.push_back(N + (1u << (sh - 1)) - 1);
+        }
+        // twenty /31 and /32 prefixes inside one /26: a split node whose
+        // second chunk is the last one (128 or 64 entries at /17 and /18)
+        const uint32_t M = 0x0A300040u;
+        for (uint32_t i = 0; i < 20; i++) {
+            const bool p31 = i % 5 == 4;
+            v.push_back({M + 3 * i - (p31 ? (3 * i) & 1 : 0), (uint8_t)(p31 ? 31 : 32),
+                         (i & 1 ? wide : 0) + 2000 + i});
+        }
+        for (uint32_t o = 0; o < 66; o++)
+            pr.push_back(M - 1 + o);
+        // directory indices of all ones and all zeros
+        v.push_back({0xFFFFFF00u, 24, 31});
+        v.push_back({0xFFFFFFFFu, 32, wide + 32});
+        v.push_back({0, (uint8_t)(D + 1), 33});
+        v.push_back({1, 32, 34});
+        for (uint32_t a : {0xFFFFFFFFu, 0xFFFFFFFEu, 0xFFFFFF00u, 0xFFFFFEFFu, 0xFFFFC000u, 0u,
+                           1u, 2u, (1u << (sh - 1)) - 1, 1u << (sh - 1), 1u << sh})
+            pr.push_back(a);
+        char nm[32];
+        snprintf(nm, sizeof nm, "edges-%d", D);
+        fail |= lpm4_case(nm, v, gen, 5000, pr);
     }
     return fail;
 }
@@ -643,6 +720,8 @@ int main(int argc, char **argv)
     if (argc > 1 && !strcmp(argv[1], "kat"))   // the known answers alone
         return 0;
     std::mt19937 gen(12345);
+    if (argc > 1 && !strcmp(argv[1], "lpm4"))   // the IPv4 LPM builders alone
+        return lpm4_tests(gen);
     auto rng = [&gen]() -> uint32_t { return (uint32_t)gen(); };
     int fail = 0;
     {   // C3-like: /32../128, mass at /48 /56 /64 /128

@@ -294,7 +294,8 @@ class Datapath:
         return _stream_handle(stream)
 
     def set_option(self, option, value):
-        """cfc_set_option: L.OPT_LPM4 (ipcache layout, next commit) or
+        """cfc_set_option: L.OPT_LPM4 (ipcache layout, next commit),
+        L.OPT_LPM4_DIR_BITS (its directory width, next commit) or
         L.OPT_TIMING (per-call kernel events)."""
         L.check(self.L.cfc_set_option(self.h, option, value), "set option")
 
@@ -572,6 +573,17 @@ class Datapath:
         st = L.Stats()
         L.check(self.L.cfc_get_stats(self.h, ctypes.byref(st)), "stats")
         return {f: getattr(st, f) for f, _ in L.Stats._fields_ if f != "pad0"}
+
+
+    def lpm4_dir_stats(self):
+        """cfc_lpm4_dir_stats: what a 16, 17 and 18 bit directory of the
+        compact IPv4 layout would make of the ipcache map as it stands ->
+        ({bits: {prefixes, unresolved, bytes}}, the width auto would take)"""
+        st = (L.Lpm4DirStat * 3)()
+        auto = ctypes.c_int(0)
+        L.check(self.L.cfc_lpm4_dir_stats(self.h, st, ctypes.byref(auto)), "lpm4 dir stats")
+        return ({16 + i: {f: getattr(st[i], f) for f, _ in L.Lpm4DirStat._fields_}
+                 for i in range(3)}, auto.value)
 
 
 def host_only():

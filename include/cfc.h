@@ -172,6 +172,13 @@ int cfc_commit(cfc_ctx *ctx, void *stream);
  * L2-resident; DIR-24-8 is the classic 64 MiB table (Infinity-Cache
  * resident), also used when the compact layout's offsets would overflow.
  * Lookups give the same result in every layout.
+ * CFC_OPT_LPM4_DIR_BITS: width of the compact layout's directory, applied at
+ * the next commit: 16, 17 or 18 address bits index it (1, 2 or 4 MiB), and a
+ * wider one resolves more lookups with its single load.  0 (default) = auto:
+ * the narrowest width that leaves few of the table's prefixes to a second
+ * load, within a byte budget that keeps the layout L2-resident
+ * (cfc_stats.lpm4_kib shows what was taken).  Lookups give the same result
+ * at every width.
  * CFC_OPT_TIMING: 1 = record HIP events around the kernels of every
  * cfc_classify_* call (read back with cfc_timing_collect).
  * CFC_OPT_CT_APPLY: where cfc_ct_apply_v4 runs: DEVICE (default) applies the
@@ -194,6 +201,7 @@ int cfc_commit(cfc_ctx *ctx, void *stream);
 #define CFC_CT_APPLY_DEVICE 0
 #define CFC_CT_APPLY_HOST 1
 #define CFC_OPT_CT_EVICT 4
+#define CFC_OPT_LPM4_DIR_BITS 5
 int cfc_set_option(cfc_ctx *ctx, int option, int64_t value);
 
 /* ---------------------------------------------------------------- datapath */
@@ -786,6 +794,19 @@ typedef struct {
     double count_v6_ms;
 } cfc_timing;
 int cfc_timing_collect(cfc_ctx *ctx, cfc_timing *out);
+
+/* What each directory width of the compact IPv4 layout would make of the
+ * ipcache map as it stands (CFC_OPT_LPM4_DIR_BITS; works on a host-only
+ * context): st[0..2] for 16, 17 and 18 bits.  unresolved = prefixes the
+ * directory's one load cannot resolve (per entry, those longer than the
+ * directory beyond the two it holds inline); bytes = directory + chunks +
+ * lists.  *auto_bits = the width auto would take. */
+typedef struct {
+    uint64_t prefixes;
+    uint64_t unresolved;
+    uint64_t bytes;
+} cfc_lpm4_dir_stat;
+int cfc_lpm4_dir_stats(cfc_ctx *ctx, cfc_lpm4_dir_stat st[3], int *auto_bits);
 
 #ifdef __cplusplus
 }
