@@ -2896,8 +2896,8 @@ constexpr uint16_t CTB_RX_CLOSING = 1, CTB_TX_CLOSING = 2, CTB_NAT46 = 4, CTB_LB
 constexpr uint32_t CT_LIFETIME_TCP = 21600, CT_LIFETIME_NONTCP = 60, CT_SYN_TIMEOUT = 60,
                    CT_CLOSE_TIMEOUT = 10, CT_REPORT_INTERVAL = 5;
 
-// __ct_update_timeout (conntrack.h:125-185)
-void ct_upd(CtEntry &e, uint32_t now, uint32_t lifetime, int dir, uint8_t flags)
+// __ct_update_timeout (conntrack.h:125-185) -> whether the hit is reported
+bool ct_upd(CtEntry &e, uint32_t now, uint32_t lifetime, int dir, uint8_t flags)
 {
     e.lifetime = now + lifetime;
     uint8_t &acc = dir == 1 ? e.rx_flags_seen : e.tx_flags_seen;
@@ -2906,10 +2906,12 @@ void ct_upd(CtEntry &e, uint32_t now, uint32_t lifetime, int dir, uint8_t flags)
     if (last + CT_REPORT_INTERVAL < now || acc != seen) {
         last = now;
         acc = seen;
+        return true;
     }
+    return false;
 }
 // ct_update_timeout (:191-205); syn is bit 0 of TCP byte 12 (union tcp_flags)
-void ct_upd_timeout(CtEntry &e, uint32_t now, bool is_tcp, int dir, bool syn,
+bool ct_upd_timeout(CtEntry &e, uint32_t now, bool is_tcp, int dir, bool syn,
                     uint8_t flags)
 {
     uint32_t lifetime = CT_LIFETIME_NONTCP;
@@ -2918,15 +2920,19 @@ void ct_upd_timeout(CtEntry &e, uint32_t now, bool is_tcp, int dir, bool syn,
             e.bits |= CTB_SEEN_NON_SYN;
         lifetime = (e.bits & CTB_SEEN_NON_SYN) ? CT_LIFETIME_TCP : CT_SYN_TIMEOUT;
     }
-    ct_upd(e, now, lifetime, dir, flags);
+    return ct_upd(e, now, lifetime, dir, flags);
 }
 
 // What __ct_lookup (:221-285) does to a hit entry, applied in header order
 // at the batch's clock: timeouts, report times, seen flags, the closing
 // bits of ACTION_CREATE / ACTION_CLOSE; with count, CONNTRACK_ACCOUNTING
-// for a hit the device did not see (a flow created earlier in the batch)
-void ct_hit_update(Map *m, Map::Entry &me, int action, int dir, bool count,
-                   uint32_t len, uint32_t now, bool is_tcp, bool syn, uint8_t flags)
+// for a hit the device did not see (a flow created earlier in the batch).
+// -> the lookup's *monitor (kern_common.hpp ct_monitor_of): 1 for a reported
+// hit (ct_update_timeout is declared bool), 0 inside the report interval,
+// TRACE_PAYLOAD_LEN for ACTION_CLOSE
+constexpr uint32_t HOST_TRACE_PAYLOAD_LEN = 128, HOST_MTU_LEN = 1500;
+uint32_t ct_hit_update(Map *m, Map::Entry &me, int action, int dir, bool count,
+                       uint32_t len, uint32_t now, bool is_tcp, bool syn, uint8_t flags)
 {
     CtEntry e;
     memcpy(&e, me.val.data(), sizeof(e));
@@ -2935,21 +2941,24 @@ void ct_hit_update(Map *m, Map::Entry &me, int action, int dir, bool count,
         (dir == 1 ? e.rx_bytes : e.tx_bytes) += len;
     }
     auto alive = [&] { return !(e.bits & CTB_RX_CLOSING) || !(e.bits & CTB_TX_CLOSING); };
+    uint32_t mon = 0;
     if (alive())
-        ct_upd_timeout(e, now, is_tcp, dir, syn, flags);
+        mon = ct_upd_timeout(e, now, is_tcp, dir, syn, flags);
     if (action == 1) {            // ACTION_CREATE re-opens a closing entry
         if (e.bits & (CTB_RX_CLOSING | CTB_TX_CLOSING)) {
             e.bits &= (uint16_t)~(CTB_RX_CLOSING | CTB_TX_CLOSING);
-            ct_upd_timeout(e, now, is_tcp, dir, syn, flags);
+            mon = ct_upd_timeout(e, now, is_tcp, dir, syn, flags);
         }
     } else if (action == 2) {     // ACTION_CLOSE: rx_closing / tx_closing
         e.bits |= dir == 1 ? CTB_RX_CLOSING : CTB_TX_CLOSING;
         if (!alive())
-            ct_upd(e, now, CT_CLOSE_TIMEOUT, dir, flags);
+            (void)ct_upd(e, now, CT_CLOSE_TIMEOUT, dir, flags);
+        mon = HOST_TRACE_PAYLOAD_LEN;
     }
     memcpy(&me.val[0], &e, sizeof(e));
     m->touched[me.key] |= TOUCH_VALUE;
     m->gen++;
+    return mon;
 }
 
 // ---- load balancing on the host CT maps (cfc_ct_apply_v4 with a load
@@ -4056,6 +4065,17 @@ int ct_apply_one(cfc_ctx *c, int family, const Hdr *in, const cfc_out *out, int 
             hipStreamSynchronize(s) != hipSuccess)
             return -EIO;
     }
+    // the event words: a trace's CT result and monitor length are re-decided
+    // in packet order, as the device apply does (ctapply.hip k_cta_mon)
+    std::vector<uint32_t> nt;
+    if (out->notify) {
+        nt.resize(n);
+        if (hipMemcpyAsync(nt.data(), out->notify, 4 * n, hipMemcpyDeviceToHost, s) !=
+                hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess)
+            return -EIO;
+    }
+    bool nt_changed = false;
     CtApply A(c, family);
     const LbHost L(c);
     const bool lbon = family == 4 && L.on();
@@ -4201,6 +4221,22 @@ int ct_apply_one(cfc_ctx *c, int family, const Hdr *in, const cfc_out *out, int 
         if (x.drop)
             continue;
         const int last = (cb & (CFC_CT_DONE << 4)) ? 1 : 0;
+        // the stage a trace reports (local delivery's when it ran): its
+        // result and *monitor in packet order
+        auto trace = [&](int st, int res, uint32_t mon, uint32_t td, uint32_t ts, bool eg) {
+            if (nt.empty() || st != last || ((nt[i] >> 16) & 0xF) < CFC_NT_TRACE)
+                return;
+            if (res == 0)   // CT_NEW
+                mon = HOST_TRACE_PAYLOAD_LEN;
+            // conn_is_dns (conntrack.h:585-586); ipv6_l3_from_lxc sets
+            // TRACE_PAYLOAD_LEN after its ct_create6 (bpf_lxc.c:248)
+            if ((res >= 2 ? td : ts) == 0x3500u && !(family == 6 && eg && res == 0))
+                mon = HOST_MTU_LEN;
+            const uint32_t cls = mon == 0 ? 0u : mon == HOST_MTU_LEN ? 2u : mon == 1u ? 3u : 1u;
+            const uint32_t w = (nt[i] & 0x000FFFFFu) | (uint32_t)res << 20 | cls << 22;
+            nt_changed |= w != nt[i];
+            nt[i] = w;
+        };
         for (int st = 0; st < 2; st++) {
             const uint8_t cs = (uint8_t)(cb >> (4 * st));
             if (!(cs & CFC_CT_DONE))
@@ -4274,8 +4310,8 @@ int ct_apply_one(cfc_ctx *c, int family, const Hdr *in, const cfc_out *out, int 
             if (b >= 2) {                       // CT_REPLY / CT_RELATED
                 auto it = m->kv.find(k1);
                 if (it != m->kv.end()) {
-                    ct_hit_update(m, it->second, action, dir, fresh(m, k1), len, now,
-                                  is_tcp, syn, tflags);
+                    trace(st, b, ct_hit_update(m, it->second, action, dir, fresh(m, k1), len,
+                                               now, is_tcp, syn, tflags), td, ts, eg);
                     if (lbon && eg) {   // the egress reply's reverse NAT
                         CtEntry e;
                         memcpy(&e, it->second.val.data(), sizeof(e));
@@ -4290,8 +4326,8 @@ int ct_apply_one(cfc_ctx *c, int family, const Hdr *in, const cfc_out *out, int 
             } else if (b == 1) {                // CT_ESTABLISHED
                 auto it = m->kv.find(k2);
                 if (it != m->kv.end()) {
-                    ct_hit_update(m, it->second, action, dir, fresh(m, k2), len, now,
-                                  is_tcp, syn, tflags);
+                    trace(st, b, ct_hit_update(m, it->second, action, dir, fresh(m, k2), len,
+                                               now, is_tcp, syn, tflags), td, ts, eg);
                     if (dropped) {              // ct_delete4/6
                         ct_drop_counts(c, m, k2, s);
                         note(m, k2);
@@ -4301,10 +4337,12 @@ int ct_apply_one(cfc_ctx *c, int family, const Hdr *in, const cfc_out *out, int 
             } else if (csn & CFC_CT_CREATE) {
                 auto it = m->kv.find(k2);
                 if (it != m->kv.end()) {        // created earlier in this batch
-                    ct_hit_update(m, it->second, action, dir, true, len, now, is_tcp,
-                                  syn, tflags);
+                    (void)ct_hit_update(m, it->second, action, dir, true, len, now, is_tcp,
+                                        syn, tflags);
+                    trace(st, b, 0, td, ts, eg);
                     continue;
                 }
+                trace(st, b, 0, td, ts, eg);
                 // ct_create4/6 (conntrack.h:615-662, :691-772): timeouts
                 // with seen_flags.syn = is_tcp (lower_bits stay 0)
                 CtEntry e{};
@@ -4349,11 +4387,16 @@ int ct_apply_one(cfc_ctx *c, int family, const Hdr *in, const cfc_out *out, int 
                 if (m->kv.count(ki))            // overwritten
                     ct_drop_counts(c, m, ki, s);
                 put_new(m, ki, e);
+            } else {
+                trace(st, b, 0, td, ts, eg);
             }
         }
     }
     if (ct_changed &&
         hipMemcpyAsync(out->ct, ct.data(), n, hipMemcpyHostToDevice, s) != hipSuccess)
+        return -EIO;
+    if (nt_changed &&
+        hipMemcpyAsync(out->notify, nt.data(), 4 * n, hipMemcpyHostToDevice, s) != hipSuccess)
         return -EIO;
     if (hipStreamSynchronize(s) != hipSuccess)
         return -EIO;

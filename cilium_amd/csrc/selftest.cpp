@@ -267,6 +267,48 @@ static int selfcut_tests()
     return fail;
 }
 
+// `kat selfcut`: a fixed pseudo-random row list per family and the cuts the
+// rule gives, for the restatement in tests/self_edges.py (cut_rule).  Lines
+// `selfcut family <v6> <n_own>`, `selfcut row <x> <y> <z> <w>`, `selfcut cut
+// <x>`, decimal.  Few ports, so keys collide; bits above the protocol byte
+// of the meta word and above the type byte of an ICMP L4 word are noise the
+// rule must mask; two own addresses (w 0, 1) and two loopback ones (2, 3).
+static void selfcut_kats()
+{
+    uint32_t s = 0x5e1fc075u;
+    auto lcg = [&s]() -> uint32_t {
+        s = s * 1664525u + 1013904223u;
+        return s >> 8;
+    };
+    const uint32_t PORTS[] = {1000, 1001, 80, 53, 0xE803, 0x5000};
+    const uint32_t TYPES4[] = {0, 8, 3, 11, 12, 13, 1, 4, 5};
+    const uint32_t TYPES6[] = {128, 129, 1, 2, 3, 4, 133, 135, 0, 5};
+    for (int v6 = 0; v6 < 2; v6++) {
+        const uint32_t n_own = 2;
+        std::vector<Row> rows;
+        uint32_t x = lcg() % 3;
+        for (int i = 0; i < 400; i++, x += 1 + lcg() % 3) {
+            const uint32_t sel = lcg() % 16;
+            const uint32_t proto = sel < 7 ? 6 : sel < 11 ? 17 : sel < 15 ? (v6 ? 58 : 1) : 47;
+            uint32_t pt = PORTS[lcg() % 6] | PORTS[lcg() % 6] << 16;
+            if (proto == 1)
+                pt = TYPES4[lcg() % 9] | lcg() << 8;
+            else if (proto == 58)
+                pt = TYPES6[lcg() % 10] | lcg() << 8;
+            uint32_t w = lcg() % 48;
+            w = w < 4 ? w : w & 1;
+            rows.push_back({x, pt, proto | lcg() << 8, w});
+        }
+        std::vector<uint64_t> cuts;
+        self_cut_rule(rows, n_own, v6 != 0, &cuts);
+        printf("selfcut family %d %u\n", v6, n_own);
+        for (const Row &r : rows)
+            printf("selfcut row %u %u %u %u\n", r.x, r.y, r.z, r.w);
+        for (uint64_t c : cuts)
+            printf("selfcut cut %llu\n", (unsigned long long)c);
+    }
+}
+
 static uint32_t brute(const std::vector<Pfx6> &pfx, const uint32_t w[4])
 {
     int best = -1;
@@ -716,6 +758,10 @@ static void hash_kats()
 
 int main(int argc, char **argv)
 {
+    if (argc > 2 && !strcmp(argv[1], "kat") && !strcmp(argv[2], "selfcut")) {
+        selfcut_kats();   // the cut rule's known answers alone
+        return 0;
+    }
     hash_kats();
     if (argc > 1 && !strcmp(argv[1], "kat"))   // the known answers alone
         return 0;

@@ -185,7 +185,9 @@ int cfc_commit(cfc_ctx *ctx, void *stream);
  * batch's CT writes to the device CT table in place and keeps the host's
  * view of the CT maps lazily (synchronised when a CT map is next read or
  * written through this API, or at cfc_counters_sync); HOST walks the batch
- * on the host.  Both give the same maps.
+ * on the host.  Both give the same maps and CT bytes, and both re-decide a
+ * trace word's CT result and monitor length in packet order (the host walk
+ * for the batch's own stages, not for a NAT hop batch's).
  * CFC_OPT_CT_EVICT: 1 (default) = a batch whose creates would take an IPv4
  * CT map past its max_entries stays on the device: the map's entries
  * closest to expiry that the batch's lookups did not hit are deleted first

@@ -2587,6 +2587,8 @@ static void ct_apply(cfo_t *o, int alen, int mode, uint16_t ep_lxc, size_t n,
         }
         const epinfo *dst = lxc_lookup(o, alen == 4 ? 1 : 2,
                                        alen == 4 ? (const uint8_t *)&pda4 : pda6);
+        uint8_t wk[3][CTK];   /* (pass 1) what this header's egress stage creates */
+        int wn = 0;
         for (int s = 0; s < 2; s++) {
             if (s == 1)   /* (a reverse NAT may have moved it) */
                 dst = lxc_lookup(o, alen == 4 ? 1 : 2,
@@ -2684,9 +2686,28 @@ static void ct_apply(cfo_t *o, int alen, int mode, uint16_t ep_lxc, size_t n,
             }
             if (pass == 1) {   /* CONNTRACK_ACCOUNTING of the lookup hits */
                 const int64_t e = b >= CT_REPLY ? e1 : b == CT_ESTABLISHED ? e2 : -1;
-                if (e < 0 && b != CT_NEW)
+                /* the keys this header's egress stage writes anew: ct_create4
+                 * runs before the local delivery's lookup (bpf_lxc.c:555,
+                 * 627), so the destination's hit on one of them — a
+                 * looped-back flow's reply entry written over an earlier
+                 * flow's, conntrack.h:725-748 — is counted on the entry as
+                 * written (pass 2), not on the one it replaces */
+                if (egress_stage && b == CT_NEW && (cs & CTO_CREATE1) && e2 < 0) {
+                    ctstate_t st0 = {0, 0, 0, 0, 0, 0};
+                    if (lbv && alen == 4)
+                        st0 = (ctstate_t){x.rev_nat, x.slave, x.loopback, x.addr,
+                                          x.svc_addr, 0};
+                    if (lbv && alen == 16)
+                        st0 = (ctstate_t){x6.rev_nat, x6.slave, 0, 0, 0, 0};
+                    struct ctent we[3];
+                    wn = ct_create_entries(o, k2, alen, dir, len[i], sec, &st0, wk, we);
+                }
+                int own = 0;
+                for (int j = 0; j < wn && s == 1 && e >= 0; j++)
+                    own |= !memcmp(wk[j], b >= CT_REPLY ? k1 : k2, CTK);
+                if ((e < 0 && b != CT_NEW) || own)
                     fresh[2 * i + s] = 1;
-                if (e >= 0) {
+                if (e >= 0 && !own) {
                     struct ctent *x = &o->ct_ents[e];
                     if (dir == CT_INGRESS) {
                         x->rx_packets++;
