@@ -655,7 +655,7 @@ struct NotifyArgs {
     const uint32_t *ports;
     const uint32_t *saddr;   // v4: n words; v6: n x 4 words
     const uint32_t *daddr;
-    const uint32_t *hash;    // skb->hash per header (v4), or NULL: flow_hash
+    const uint32_t *hash;    // skb->hash per header (v4 and v6), or NULL: flow_hash
     uint64_t n;
     int family;              // 4 or 6
     int mode;
