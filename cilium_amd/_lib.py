@@ -16,6 +16,8 @@ HF_FRAG, HF_TCP_CLOSE, HF_EXTHDR = 0x100, 0x200, 0x400
 DROP_PREFILTER, VERDICT_PUNT = -1, -2
 OPT_LPM4, OPT_TIMING, OPT_CT_APPLY, OPT_CT_EVICT = 1, 2, 3, 4
 OPT_LPM4_DIR_BITS = 5
+OPT_POL_PLACEMENT = 6
+POL_PLACEMENT_AUTO, POL_PLACEMENT_LINEAR, POL_PLACEMENT_DIRECT = 0, 1, 2
 CT_APPLY_DEVICE, CT_APPLY_HOST = 0, 1
 LPM4_AUTO, LPM4_DIR24_8, LPM4_TRIE = 0, 1, 2
 
@@ -35,6 +37,7 @@ EXPORTS = (
     "cfc_map_dump", "cfc_ct_gc",
     "cfc_proxy_entries_v4", "cfc_proxy_entries_v6",
     "cfc_proxy_apply_v4", "cfc_proxy_apply_v6", "cfc_lpm4_dir_stats",
+    "cfc_pol_placement",
 )
 # CT byte (cfc_out.ct): per stage (bits 0-3, then 4-7 for the destination's
 # ingress lookup after egress local delivery)
@@ -216,6 +219,8 @@ def lib():
     L.cfc_timing_collect.argtypes = [vp, ctypes.POINTER(Timing)]
     if hasattr(L, "cfc_lpm4_dir_stats"):   # (a CFC_LIB build of an older tree has none)
         L.cfc_lpm4_dir_stats.argtypes = [vp, ctypes.POINTER(Lpm4DirStat), pint]
+    if hasattr(L, "cfc_pol_placement"):
+        L.cfc_pol_placement.argtypes = [vp, pint, pint]
     L.cfc_strerror.argtypes = [i32]
     L.cfc_strerror.restype = ctypes.c_char_p
     _lib = L

@@ -61,6 +61,10 @@ struct GPf {           // prefilter
 struct GEp {           // endpoints + policy (+ the counter layout)
     DevBuf lxc4, lxc6, pol, polbloom;
     std::vector<PolSlot> pol_host;    // for in-place proxy-port patches
+    // direct placement: the displacement bytes (on the device they follow
+    // the Bloom words in polbloom); empty: linear probing
+    std::vector<uint8_t> pol_disp;
+    uint32_t pol_max_disp = 0;
     uint32_t lxc4_mask = 0, lxc6_mask = 0, pol_bloom_words = 0, n_eps = 0, n_eps6 = 0;
     bool lxc4_lds = false, lxc6_lds = false;
     std::unordered_map<int, PolLoc> pol_loc;
@@ -323,6 +327,7 @@ void group_sigs(cfc_ctx *c, uint64_t sig[NGROUPS])
     auto mix = [&](int g, uint64_t v) { sig[g] = (sig[g] ^ v) * 1099511628211ull; };
     mix(0, (uint64_t)c->opts.lpm4);
     mix(0, (uint64_t)c->opts.lpm4_dir_bits);
+    mix(2, (uint64_t)c->opts.pol_placement);
     mix(2, c->seclabel_gen);
     for (auto &kv : c->maps) {
         const Map *m = kv.second.get();
@@ -774,8 +779,16 @@ std::shared_ptr<GEp> build_ep(cfc_ctx *c, HostImage &img, const std::vector<Map 
                               hipStream_t s, int *rc)
 {
     auto g = std::make_shared<GEp>();
+    // the policy Bloom words, then (direct placement) a displacement byte each
+    std::vector<uint32_t> polb = img.pol_bloom;
+    if (img.pol_direct) {
+        polb.resize(polb.size() + img.pol_disp.size() / 4);
+        memcpy(polb.data() + img.pol_bloom.size(), img.pol_disp.data(), img.pol_disp.size());
+        g->pol_disp = img.pol_disp;
+        g->pol_max_disp = img.pol_max_disp;
+    }
     if ((*rc = upload_vec(g->lxc4, img.lxc4, s)) || (*rc = upload_vec(g->pol, img.pol, s)) ||
-        (*rc = upload_vec(g->polbloom, img.pol_bloom, s)) ||
+        (*rc = upload_vec(g->polbloom, polb, s)) ||
         (*rc = upload_vec(g->lxc6, img.lxc6, s)))
         return nullptr;
     g->lxc4_mask = img.lxc4_mask;
@@ -789,7 +802,7 @@ std::shared_ptr<GEp> build_ep(cfc_ctx *c, HostImage &img, const std::vector<Map 
     g->pol_loc = std::move(img.pol_loc);
     g->ctr_owner = std::move(img.ctr_owner);
     g->bytes = sizeof(LxcSlot) * img.lxc4.size() + sizeof(PolSlot) * img.pol.size() +
-               4ull * img.pol_bloom.size() + sizeof(Lxc6Slot) * img.lxc6.size();
+               4ull * polb.size() + sizeof(Lxc6Slot) * img.lxc6.size();
     // drop notifications: {SECLABEL, ifindex} by LXC_ID (struct
     // endpoint_info), and the SECLABELs the epoch's verdicts use
     g->seclabel = c->seclabel;
@@ -933,6 +946,7 @@ void assemble(Epoch &E)
     T.pol = (const PolSlot *)D.pol.p;
     T.pol_bloom = (const uint32_t *)D.polbloom.p;
     T.pol_bloom_words = D.pol_bloom_words;
+    T.pol_direct = !D.pol_disp.empty();
     T.n_ctr = (uint32_t)D.ctr_owner.size();
     // (a table a device apply may fill counts even while empty)
     T.ct4 = (C.t4.n || C.t4.slots) ? (const Ct4Slot *)C.t4.key.p : nullptr;
@@ -1040,12 +1054,9 @@ unsigned patch_touched(cfc_ctx *c, unsigned groups, hipStream_t s)
                 if (((uint8_t)t.first[7] & 0xFE) != 0)
                     continue;   // not in the device table (flatten.cpp)
                 const uint32_t mask = loc->second.mask, base = loc->second.base;
-                uint32_t sl = pol_slot(pol_key_pre((uint32_t)key, (uint32_t)(key >> 32)), mask);
                 PolSlot *tab = E.ep->pol_host.data() + base;
-                uint32_t n = 0;
-                while (tab[sl].key != key && tab[sl].key != POL_EMPTY && n++ <= mask)
-                    sl = (sl + 1) & mask;
-                if (tab[sl].key != key) {
+                const uint32_t sl = pol_find_slot(tab, base, mask, key, E.ep->pol_disp);
+                if (sl == EMPTY) {
                     groups |= GROUP_ENDPOINTS;
                     break;
                 }
@@ -1275,6 +1286,8 @@ int commit_locked(cfc_ctx *c, hipStream_t s)
     img.ct_min4 = c->ctf[0].min_slots;
     img.ct_min6 = c->ctf[1].min_slots;
     build_image(ms, c->opts, &img, groups);
+    if (c->opts.pol_placement == POL_PLACE_DIRECT && img.pol_direct_failed)
+        return -ENOSPC;   // (nothing changed: the epoch and the journals stay)
 
     auto E = std::make_shared<Epoch>();
     E->id = ++c->epoch_seq;
@@ -1428,6 +1441,12 @@ int cfc_open(int device, cfc_ctx **out)
     }
     auto *c = new cfc_ctx();
     c->device = device;
+    // CFC_POL_PLACEMENT=linear|direct: the option's starting value (A/B runs
+    // of programs that set no option)
+    if (const char *e = getenv("CFC_POL_PLACEMENT"))
+        c->opts.pol_placement = !strcmp(e, "linear")   ? POL_PLACE_LINEAR
+                                : !strcmp(e, "direct") ? POL_PLACE_DIRECT
+                                                       : POL_PLACE_AUTO;
     if (device != CFC_DEVICE_NONE) {
         hipDeviceProp_t p;
         if (hipGetDeviceProperties(&p, device) == hipSuccess &&
@@ -1498,6 +1517,11 @@ int cfc_set_option(cfc_ctx *c, int option, int64_t value)
             return -EINVAL;
         c->opts.lpm4_dir_bits = (int)value;   // the next commit rebuilds
         return 0;
+    case CFC_OPT_POL_PLACEMENT:
+        if (value < CFC_POL_PLACEMENT_AUTO || value > CFC_POL_PLACEMENT_DIRECT)
+            return -EINVAL;
+        c->opts.pol_placement = (int)value;   // the next commit rebuilds
+        return 0;
     case CFC_OPT_TIMING:
         if (value != 0 && value != 1)
             return -EINVAL;
@@ -1518,6 +1542,21 @@ int cfc_set_option(cfc_ctx *c, int option, int64_t value)
     default:
         return -EINVAL;
     }
+}
+
+int cfc_pol_placement(cfc_ctx *c, int *placement, int *max_disp)
+{
+    if (!c)
+        return -EINVAL;
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    if (!c->epoch)
+        return -ENOENT;
+    const GEp &D = *c->epoch->ep;
+    if (placement)
+        *placement = D.pol_disp.empty() ? CFC_POL_PLACEMENT_LINEAR : CFC_POL_PLACEMENT_DIRECT;
+    if (max_disp)
+        *max_disp = (int)D.pol_max_disp;
+    return 0;
 }
 
 int cfc_lpm4_dir_stats(cfc_ctx *c, cfc_lpm4_dir_stat st[3], int *auto_bits)

@@ -453,7 +453,7 @@ __device__ __forceinline__ void r4_verdict(const DevTables &T, const Lds &S,
     uint32_t ctb = h.ct_byte;
     const bool frag = (h.mt & CFC_HF_FRAG) != 0;
     const uint32_t proto = h.mt & 0xFF;
-    const PolicyResult pr = policy_resolve(T, h.pbase, h.pmask, h.P);
+    const PolicyResult pr = policy_resolve(T, S, h.pbase, h.pmask, h.P);
     const int mdir = EGR ? METRIC_EGRESS : METRIC_INGRESS;
     const bool ifx = (h.rec.w & LXC_IFINDEX) != 0;
     int v = pr.verdict;
@@ -641,14 +641,19 @@ __device__ __forceinline__ void r4_verdict(const DevTables &T, const Lds &S,
 }
 
 // LDS image of one launch: the metrics block, then the tables copied in.
+// (pol_disp: the displacement bytes of a direct policy placement, behind the
+// policy Bloom words in the tables and in the image)
 struct LdsPlan {
-    uint32_t lxc_slots, pf_words, pol_words;
+    uint32_t lxc_slots, pf_words, pol_words, pol_disp;
     __host__ __device__ size_t bytes() const
     {
         return 8ull * LDS_MET_U64 + 16ull * lxc_slots + 4ull * pf_words +
-               4ull * pol_words;
+               4ull * pol_words + pol_disp;
     }
 };
+// a direct placement the builder accepted (layout.h POL_DIRECT_LDS) fits the image
+static_assert(8 * LDS_MET_U64 + 4 * PF_BLOOM_MAX_WORDS + POL_DIRECT_LDS <= LDS_PER_WG ||
+              CFC_WG_PER_CU != 2, "POL_DIRECT_LDS assumes 80 KiB per workgroup");
 
 __host__ LdsPlan lds_plan(const DevTables &T)
 {
@@ -656,6 +661,7 @@ __host__ LdsPlan lds_plan(const DevTables &T)
     p.lxc_slots = (T.lxc4 && T.lxc4_lds) ? T.lxc4_mask + 1 : 0;
     p.pf_words = T.pf_bloom ? T.pf_bloom_words : 0;
     p.pol_words = T.pol_bloom ? T.pol_bloom_words : 0;
+    p.pol_disp = T.pol_direct ? p.pol_words : 0;
     return p;
 }
 
@@ -703,6 +709,7 @@ __global__ __launch_bounds__(BLOCK, WAVES_PER_SIMD) void k_classify_v4(
             __builtin_assume(T.pf_fix != nullptr);
     }
     // LDS image (uint4 units): metrics | endpoint slots | pf Bloom | pol Bloom
+    // | the policy displacement bytes
     unsigned long long *s_met = lds_met();
     Lds S;
     S.lxc_off = LDS_MET_U64 / 2;
@@ -713,6 +720,7 @@ __global__ __launch_bounds__(BLOCK, WAVES_PER_SIMD) void k_classify_v4(
     S.lxc = FAST || L.lxc_slots != 0;
     S.pfb = FAST || L.pf_words != 0;
     S.polb = FAST || L.pol_words != 0;
+    S.pold = L.pol_disp != 0;
     S.pfb_mask = L.pf_words - 1;
     S.polb_mask = L.pol_words - 1;
     for (uint32_t j = threadIdx.x; j < (uint32_t)LDS_MET_U64; j += BLOCK)
@@ -724,7 +732,7 @@ __global__ __launch_bounds__(BLOCK, WAVES_PER_SIMD) void k_classify_v4(
     lds_copy(cfc_smem + pf4, reinterpret_cast<const uint4 *>(T.pf_bloom),
              L.pf_words / 4);
     lds_copy(cfc_smem + pol4, reinterpret_cast<const uint4 *>(T.pol_bloom),
-             L.pol_words / 4);
+             (L.pol_words + L.pol_disp / 4) / 4);
     __syncthreads();
 
     constexpr bool EGR = MODE == CFC_MODE_EGRESS;

@@ -179,20 +179,27 @@ __device__ __forceinline__ bool ct6_new_dport(uint32_t proto, uint32_t ports,
 // LDS image of a v6 launch: metrics | endpoint slots | policy Bloom | the
 // length lists of the three Lpm6 tables (ipcache, prefilter fix, dyn): a
 // lookup reads its next length from LDS, not by a dependent global load
+// (pol_disp: the displacement bytes of a direct policy placement)
 struct LdsPlan6 {
-    uint32_t lxc_slots, pol_words, pf_words, nlens;
+    uint32_t lxc_slots, pol_words, pol_disp, pf_words, nlens;
     __host__ __device__ size_t bytes() const
     {
-        return 8ull * LDS_MET6_U64 + 32ull * lxc_slots + 4ull * pol_words + 4ull * pf_words +
-               4ull * nlens;
+        return 8ull * LDS_MET6_U64 + 32ull * lxc_slots + 4ull * pol_words + pol_disp +
+               4ull * pf_words + 4ull * nlens;
     }
 };
+// a direct placement the builder accepted (layout.h POL_DIRECT_LDS) fits the image with
+// the largest prefilter filter and three full length lists
+static_assert(8 * LDS_MET6_U64 + 4 * 3 * 128 + 4 * PF_BLOOM_MAX_WORDS + POL_DIRECT_LDS <=
+                      LDS_PER_WG || CFC_WG_PER_CU != 2,
+              "POL_DIRECT_LDS assumes 80 KiB per workgroup");
 
 __host__ LdsPlan6 lds_plan6(const DevTables &T)
 {
     LdsPlan6 p;
     p.lxc_slots = (T.lxc6 && T.lxc6_lds) ? T.lxc6_mask + 1 : 0;
     p.pol_words = T.pol_bloom ? T.pol_bloom_words : 0;
+    p.pol_disp = T.pol_direct ? p.pol_words : 0;
     p.pf_words = T.pf6_bloom ? T.pf6_bloom_words : 0;
     p.nlens = T.ipc6.nlen + T.pf6_fix.nlen + T.pf6_dyn.nlen;
     if (p.bytes() > LDS_PER_WG)   // (the prefilter's filter is an optimisation: drop it first)
@@ -270,19 +277,20 @@ __global__ __launch_bounds__(BLOCK, WAVES_PER_SIMD) void k_classify_v6(
 {
     constexpr bool XDP = MODE == CFC_MODE_XDP || MODE == CFC_MODE_FULL;
     constexpr bool EGR = MODE == CFC_MODE_EGRESS;
-    // LDS image (uint4 units): metrics | endpoint slots | pol Bloom |
-    // prefilter Bloom | the length lists
+    // LDS image (uint4 units): metrics | endpoint slots | pol Bloom | the
+    // policy displacement bytes | prefilter Bloom | the length lists
     unsigned long long *s_met = lds_met();
     const uint32_t lxc_off = LDS_MET6_U64 / 2;
     const uint32_t pol4 = lxc_off + 2 * L.lxc_slots;
     const bool lxc_lds = L.lxc_slots != 0;
     Lds S;
-    const uint32_t pf4 = pol4 + L.pol_words / 4;
+    const uint32_t pf4 = pol4 + (L.pol_words + L.pol_disp / 4) / 4;
     S.lxc = false;
     S.pfb = L.pf_words != 0;
     S.pfb_off = 4 * pf4;
     S.pfb_mask = L.pf_words - 1;
     S.polb = L.pol_words != 0;
+    S.pold = L.pol_disp != 0;
     S.polb_off = 4 * pol4;
     S.polb_mask = L.pol_words - 1;
     for (uint32_t j = threadIdx.x; j < (uint32_t)LDS_MET6_U64; j += BLOCK)
@@ -292,7 +300,7 @@ __global__ __launch_bounds__(BLOCK, WAVES_PER_SIMD) void k_classify_v6(
     lds_copy(cfc_smem + lxc_off, reinterpret_cast<const uint4 *>(T.lxc6),
              2 * L.lxc_slots);
     lds_copy(cfc_smem + pol4, reinterpret_cast<const uint4 *>(T.pol_bloom),
-             L.pol_words / 4);
+             (L.pol_words + L.pol_disp / 4) / 4);
     lds_copy(cfc_smem + pf4, reinterpret_cast<const uint4 *>(T.pf6_bloom), L.pf_words / 4);
     // the length lists (dword offsets)
     const uint32_t lo_ipc = 4 * pf4 + L.pf_words;

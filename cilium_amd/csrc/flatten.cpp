@@ -6,7 +6,10 @@
 
 namespace cfc {
 
-static constexpr uint64_t POL_SLOTS_PER_KEY = 4;
+#ifndef CFC_POL_SLOTS_PER_KEY
+#define CFC_POL_SLOTS_PER_KEY 4   // (2: a measurement build)
+#endif
+static constexpr uint64_t POL_SLOTS_PER_KEY = CFC_POL_SLOTS_PER_KEY;
 static uint32_t pow2_at_least(uint64_t x)
 {
     uint32_t p = 1;
@@ -20,7 +23,7 @@ uint64_t HostImage::device_bytes() const
     return 4ull * (tbl24.size() + tbl8.size() + lbl_ovf.size() +
                    pf_tbl24.size() + pf_tbl8.size() + pf_fix.size() +
                    pf_bloom.size() + pol_bloom.size()) +
-           4ull * (l4d.size() + l4c.size()) + 8ull * l4l.size() +
+           4ull * (l4d.size() + l4c.size()) + 8ull * l4l.size() + pol_disp.size() +
            sizeof(LxcSlot) * lxc4.size() + sizeof(PolSlot) * pol.size() +
            ipc6.bytes() + pf6_fix.bytes() + pf6_dyn.bytes() +
            sizeof(Lxc6Slot) * lxc6.size() + sizeof(Ct4Slot) * ct4.size() +
@@ -1084,6 +1087,105 @@ void build_image(const std::vector<Map *> &maps, const BuildOpts &opt,
             }
         }
     }
+
+    // ---- policy placement: direct when a displacement exists for every
+    //      bucket and its bytes fit the classify workgroups' LDS image
+    if ((groups & GROUP_ENDPOINTS) && opt.pol_placement != POL_PLACE_LINEAR &&
+        !img->pol_bloom.empty()) {
+        std::vector<PolLoc> tabs;
+        for (const auto &kv : img->pol_loc)
+            tabs.push_back(kv.second);
+        const size_t lxc4_lds = img->lxc4.size() <= LXC_LDS_MAX_SLOTS ? img->lxc4.size() : 0;
+        const size_t lxc6_lds = img->lxc6.size() <= LXC6_LDS_MAX_SLOTS ? img->lxc6.size() : 0;
+        const size_t polb = 5 * img->pol_bloom.size();   // words + bytes
+        const bool fits = sizeof(LxcSlot) * lxc4_lds + polb <= POL_DIRECT_LDS &&
+                          sizeof(Lxc6Slot) * lxc6_lds + polb <= POL_DIRECT_LDS;
+        img->pol_direct = fits && pol_place_direct(&img->pol, tabs, (uint32_t)img->pol_bloom.size(),
+                                                   &img->pol_disp, &img->pol_max_disp);
+        img->pol_direct_failed = !img->pol_direct;
+    }
+}
+
+bool pol_place_direct(std::vector<PolSlot> *pol, const std::vector<PolLoc> &tabs,
+                      uint32_t words, std::vector<uint8_t> *disp, uint32_t *max_disp)
+{
+    struct Ent {
+        uint32_t bucket, base, mask, pre;
+        PolSlot slot;
+    };
+    std::vector<Ent> ents;
+    std::vector<uint32_t> count(words, 0);
+    for (const PolLoc &t : tabs)
+        for (uint32_t s = 0; s <= t.mask; s++) {
+            const PolSlot &e = (*pol)[t.base + s];
+            if (e.key == POL_EMPTY)
+                continue;
+            const uint32_t pre = pol_key_pre((uint32_t)e.key, (uint32_t)(e.key >> 32));
+            const uint32_t b = pol_bloom_hash(pol_bloom_salt(t.base), pre) & (words - 1);
+            ents.push_back(Ent{b, t.base, t.mask, pre, e});
+            count[b]++;
+        }
+    // largest buckets first (then by word, table and key: deterministic)
+    std::sort(ents.begin(), ents.end(), [&](const Ent &a, const Ent &b) {
+        if (count[a.bucket] != count[b.bucket])
+            return count[a.bucket] > count[b.bucket];
+        if (a.bucket != b.bucket)
+            return a.bucket < b.bucket;
+        if (a.base != b.base)
+            return a.base < b.base;
+        return a.slot.key < b.slot.key;
+    });
+    PolSlot empty{};
+    empty.key = POL_EMPTY;
+    empty.ctr = EMPTY;
+    std::vector<PolSlot> out(pol->size(), empty);
+    disp->assign(words, 0);
+    *max_disp = 0;
+    for (size_t i = 0; i < ents.size();) {
+        size_t j = i;
+        while (j < ents.size() && ents[j].bucket == ents[i].bucket)
+            j++;
+        uint32_t d = 0;
+        for (; d <= POL_DISP_MAX; d++) {
+            size_t k = i;
+            for (; k < j; k++) {
+                PolSlot &at = out[ents[k].base + pol_slot_direct(ents[k].pre, d, ents[k].mask)];
+                if (at.key != POL_EMPTY)
+                    break;
+                at = ents[k].slot;
+            }
+            if (k == j)
+                break;
+            while (k-- > i)   // take this attempt's keys out again
+                out[ents[k].base + pol_slot_direct(ents[k].pre, d, ents[k].mask)] = empty;
+        }
+        if (d > POL_DISP_MAX) {
+            disp->clear();
+            *max_disp = 0;
+            return false;
+        }
+        (*disp)[ents[i].bucket] = (uint8_t)d;
+        *max_disp = std::max(*max_disp, d);
+        i = j;
+    }
+    pol->swap(out);
+    return true;
+}
+
+uint32_t pol_find_slot(const PolSlot *tab, uint32_t base, uint32_t mask, uint64_t key,
+                       const std::vector<uint8_t> &disp)
+{
+    const uint32_t pre = pol_key_pre((uint32_t)key, (uint32_t)(key >> 32));
+    if (!disp.empty()) {
+        const uint32_t b = pol_bloom_hash(pol_bloom_salt(base), pre) & ((uint32_t)disp.size() - 1);
+        const uint32_t s = pol_slot_direct(pre, disp[b], mask);
+        return tab[s].key == key ? s : EMPTY;
+    }
+    uint32_t s = pol_slot(pre, mask);
+    for (uint32_t n = 0; n <= mask && tab[s].key != POL_EMPTY; n++, s = (s + 1) & mask)
+        if (tab[s].key == key)
+            return s;
+    return EMPTY;
 }
 
 }  // namespace cfc

@@ -32,9 +32,16 @@ constexpr int L4_DIR_BITS_MIN = 16, L4_DIR_BITS_MAX = 18;
 constexpr uint64_t L4_AUTO_SHARE_NUM = 1, L4_AUTO_SHARE_DEN = 10;
 constexpr uint64_t L4_AUTO_BUDGET = 3u << 20;
 
+// Placement of the policy keys (cfc_set_option CFC_OPT_POL_PLACEMENT;
+// layout.h pol_slot_direct).  Auto takes direct when every bucket finds a
+// displacement and the displacement bytes fit the classify workgroups' LDS
+// image, else linear probing; forced direct fails the commit instead.
+enum PolPlacement { POL_PLACE_AUTO = 0, POL_PLACE_LINEAR = 1, POL_PLACE_DIRECT = 2 };
+
 struct BuildOpts {
     int lpm4 = LPM4_AUTO;
     int lpm4_dir_bits = 0;   // 0 = auto, or 16..18
+    int pol_placement = POL_PLACE_AUTO;
 };
 
 // IPv6 LPM (layout.h Lpm6), host side
@@ -95,6 +102,11 @@ struct HostImage {
     // policy
     std::vector<PolSlot> pol;
     std::vector<uint32_t> pol_bloom;
+    // direct placement: one displacement byte per Bloom word (empty: linear)
+    std::vector<uint8_t> pol_disp;
+    bool pol_direct = false;
+    bool pol_direct_failed = false;                // tried, and kept linear
+    uint32_t pol_max_disp = 0;
     std::unordered_map<int, PolLoc> pol_loc;       // lxc_id -> table
     // IPv6
     Lpm6Host ipc6, pf6_fix, pf6_dyn;
@@ -151,6 +163,20 @@ enum : unsigned {
 // (ct_local, which only depends on which CT maps exist, always is).
 void build_image(const std::vector<Map *> &maps, const BuildOpts &opt,
                  HostImage *img, unsigned groups = GROUP_ALL);
+
+// Re-place the keys of linearly built policy tables (tabs: every table of
+// pol) collision-free by hash-and-displace over `words` Bloom words
+// (layout.h pol_slot_direct): buckets largest first, each the smallest d in
+// 0..POL_DISP_MAX that puts all its keys on free slots of their own tables.
+// Entries keep their proxy port and counter index.  False, with pol
+// untouched and disp empty, when a bucket finds none (two keys of one table
+// with equal pre, or hundreds of keys to a word).
+bool pol_place_direct(std::vector<PolSlot> *pol, const std::vector<PolLoc> &tabs,
+                      uint32_t words, std::vector<uint8_t> *disp, uint32_t *max_disp);
+// the slot of `key` in the table at tab (its base and mask) under the
+// epoch's placement (disp empty: linear probing), or EMPTY
+uint32_t pol_find_slot(const PolSlot *tab, uint32_t base, uint32_t mask, uint64_t key,
+                       const std::vector<uint8_t> &disp);
 
 // exposed for host-side unit tests of the LPM builders
 struct Pfx4 {

@@ -146,6 +146,8 @@ extern __shared__ uint4 cfc_smem[];
 
 struct Lds {
     bool lxc, pfb, polb;          // which tables are in LDS
+    bool pold;                    // direct policy placement: the displacement
+                                  // bytes follow the policy Bloom words
     uint32_t lxc_off;             // uint4 index of the endpoint slots
     uint32_t pfb_off, polb_off;   // dword index of the Bloom filters
     uint32_t pfb_mask, polb_mask;
@@ -158,6 +160,10 @@ __device__ __forceinline__ unsigned long long *lds_met()
 __device__ __forceinline__ uint32_t lds_word(uint32_t off)
 {
     return reinterpret_cast<const uint32_t *>(cfc_smem)[off];
+}
+__device__ __forceinline__ uint32_t lds_byte(uint32_t off)
+{
+    return reinterpret_cast<const uint8_t *>(cfc_smem)[off];
 }
 
 // ---- compact IPv4 LPM (layout.h): walk from the directory word `e`
@@ -825,13 +831,23 @@ struct PolicyProbe {
     }
 };
 
-__device__ __forceinline__ void policy_probe_key(const DevTables &T,
+// the slot key j is looked for first: its home slot, or (direct placement)
+// the one slot the builder gave it, by the displacement byte of its bucket
+__device__ __forceinline__ uint32_t policy_key_slot(const Lds &S, uint32_t base,
+                                                    uint32_t mask, uint32_t pre)
+{
+    if (!S.pold)
+        return pol_slot(pre, mask);
+    const uint32_t w = pol_bloom_hash(pol_bloom_salt(base), pre) & S.polb_mask;
+    return pol_slot_direct(pre, lds_byte(4 * (S.polb_off + S.polb_mask + 1) + w), mask);
+}
+__device__ __forceinline__ void policy_probe_key(const DevTables &T, const Lds &S,
                                                  uint32_t base, uint32_t mask,
                                                  PolicyProbe &P)
 {
     P.j = P.maybe ? __builtin_ctz(P.maybe) : 3;
     if (P.j < 3) {
-        P.s = pol_slot(P.pre(P.j), mask);
+        P.s = policy_key_slot(S, base, mask, P.pre(P.j));
         P.v = ldt16(T.pol, (base + P.s) * 16u);
     }
 }
@@ -855,7 +871,7 @@ __device__ __forceinline__ void policy_issue(const DevTables &T, const Lds &S,
         const bool m2 = bloom_maybe(S.polb_off, S.polb_mask, pol_bloom_hash(salt, P.pre(2)));
         P.maybe &= (uint32_t)m0 | (uint32_t)m1 << 1 | (uint32_t)m2 << 2;
     }
-    policy_probe_key(T, base, mask, P);
+    policy_probe_key(T, S, base, mask, P);
 }
 
 // Returns the verdict (<0 drop) and the matched counter (or NONE).  Works
@@ -866,6 +882,7 @@ struct PolicyResult {
     uint32_t ctr;
 };
 __device__ __forceinline__ PolicyResult policy_resolve_walk(const DevTables &T,
+                                                            const Lds &S,
                                                             uint32_t base,
                                                             uint32_t mask,
                                                             const PolicyProbe &P0)
@@ -883,7 +900,7 @@ __device__ __forceinline__ PolicyResult policy_resolve_walk(const DevTables &T,
                 hit = true;
                 break;
             }
-            if (key == POL_EMPTY)
+            if (key == POL_EMPTY || S.pold)   // (direct: no neighbour to step to)
                 break;
             s = (s + 1) & mask;
             v = ldt16(T.pol, (base + s) * 16u);
@@ -896,18 +913,20 @@ __device__ __forceinline__ PolicyResult policy_resolve_walk(const DevTables &T,
         maybe &= ~(1u << j);   // a false positive of the filter
         j = maybe ? __builtin_ctz(maybe) : 3;
         if (j < 3) {
-            s = pol_slot(P0.pre(j), mask);
+            s = policy_key_slot(S, base, mask, P0.pre(j));
             v = ldt16(T.pol, (base + s) * 16u);
         }
     }
     return PolicyResult{verdict, ctr};
 }
 // The issued probe decides most headers: its slot holds the key, or is
-// empty with no other key that may exist.  Only the rest walk (a probe
-// sequence, a Bloom false positive, the next key): kept out of the common
-// path, whose wait at the walk's loop would otherwise cover every load
-// issued after the probe (vmcnt counts in issue order).
+// empty (direct placement: holds anything else) with no other key that may
+// exist.  Only the rest walk (linear placement: a probe sequence; a Bloom
+// false positive, the next key): kept out of the common path, whose wait at
+// the walk's loop would otherwise cover every load issued after the probe
+// (vmcnt counts in issue order).
 __device__ __forceinline__ PolicyResult policy_resolve(const DevTables &T,
+                                                       const Lds &S,
                                                        uint32_t base,
                                                        uint32_t mask,
                                                        const PolicyProbe &P0)
@@ -915,11 +934,12 @@ __device__ __forceinline__ PolicyResult policy_resolve(const DevTables &T,
     const uint32_t j = P0.j;
     const uint64_t key = ((uint64_t)P0.v.y << 32) | P0.v.x;
     const bool hit = j < 3 && key == P0.key(j);
-    const bool done = j >= 3 || hit || (key == POL_EMPTY && !(P0.maybe & ~(1u << j)));
+    const bool done = j >= 3 || hit ||
+                      ((key == POL_EMPTY || S.pold) && !(P0.maybe & ~(1u << j)));
     if (done)
         return hit ? PolicyResult{j == 1 ? TC_ACT_OK : (int)(P0.v.z & 0xFFFF), P0.v.w}
                    : PolicyResult{DROP_POLICY, NONE};
-    return policy_resolve_walk(T, base, mask, P0);
+    return policy_resolve_walk(T, S, base, mask, P0);
 }
 
 __device__ __forceinline__ PolicyResult policy_access(
@@ -928,7 +948,7 @@ __device__ __forceinline__ PolicyResult policy_access(
 {
     PolicyProbe P;
     policy_issue(T, S, base, mask, id, dport, proto, egress, frag, P);
-    return policy_resolve(T, base, mask, P);
+    return policy_resolve(T, S, base, mask, P);
 }
 
 // Per-thread update_metrics counts (bytes in u32: a thread sees at most

@@ -165,6 +165,21 @@ __host__ __device__ inline uint32_t pol_slot(uint32_t pre, uint32_t mask)
 {
     return pre & mask;
 }
+// Direct placement (DevTables.pol_direct; flatten.cpp pol_place_direct): the
+// table is static per epoch, so the builder places every key collision-free
+// by hash-and-displace.  A key's bucket is the word of its policy Bloom
+// query (pol_bloom_hash & (words - 1)); every bucket has one displacement
+// byte d, kept behind the filter's words, and each of its keys sits at
+// pol_slot_direct(pre, d, mask) of its own endpoint's table.  d = 0 is the
+// linear layout's home slot.  The step is odd and comes from the high half
+// of pre (double hashing): a purely additive displacement could not separate
+// two keys of one bucket that share a home slot.  A lookup is then ONE probe:
+// a slot that does not hold the key means the key is absent.
+__host__ __device__ inline uint32_t pol_slot_direct(uint32_t pre, uint32_t d, uint32_t mask)
+{
+    return (pre + d * ((pre >> 16) | 1u)) & mask;
+}
+constexpr uint32_t POL_DISP_MAX = 255;
 
 // ---- blocked Bloom filters (LDS-resident while classifying) ----------------
 // One 32-bit word per key, three bits set in it: a query is one ds_read_b32.
@@ -194,6 +209,13 @@ __host__ __device__ inline uint32_t pf_bloom_hash(uint32_t addr)
 constexpr uint32_t POL_BLOOM_MAX_WORDS = 8192;    // 32 KiB
 constexpr uint32_t PF_BLOOM_MAX_WORDS = 8192;     // 32 KiB
 constexpr uint32_t LXC_LDS_MAX_SLOTS = 512;       // 8 KiB of endpoint slots
+// What an 80 KiB workgroup image has for the endpoint slots, the policy
+// Bloom words and the displacement bytes of a direct placement together,
+// whatever the prefilter group holds (it is built on its own): the largest
+// prefilter filter, the metrics block and the IPv6 length lists (at most
+// 3 x 128 words) taken off.  The builder keeps linear probing beyond it;
+// classify.hip and classify6.hip assert their images against it.
+constexpr uint32_t POL_DIRECT_LDS = 80 * 1024 - 4 * PF_BLOOM_MAX_WORDS - 2048;
 
 // ---- IPv6 LPM: one hash table over every (prefix, length), probed longest
 // length first, screened by a blocked Bloom filter.
@@ -444,6 +466,8 @@ struct DevTables {
     uint32_t n_ctr;                // policy entries (counter slots)
     uint32_t pf_bloom_words;       // power of two, 0 = no filter
     uint32_t pol_bloom_words;      // power of two, 0 = no filter
+    uint32_t pol_direct;           // 1: direct placement; pol_bloom_words
+                                   // displacement bytes follow pol_bloom's words
     uint32_t lxc4_lds;             // 1: the endpoint table is copied to LDS
     uint32_t l4_shift;             // 32 - dir_bits of l4d (16, 15 or 14)
     // IPv6

@@ -756,8 +756,167 @@ static void hash_kats()
     }
 }
 
+// ---- direct placement of the policy keys (flatten.cpp pol_place_direct,
+// layout.h pol_slot_direct): the tables built as build_image builds them
+// (linear, 4 slots per key, at least 8), re-placed, and the lookup the device
+// performs (one probe at the bucket's displacement: the slot holds the key or
+// the key is absent) against brute force: every key found once with the
+// counter index it had, absent keys not found, nothing lost or added.
+struct PolTabs {
+    std::vector<PolSlot> pol;
+    std::vector<PolLoc> tabs;
+    std::vector<std::vector<uint64_t>> keys;
+};
+static PolTabs pol_linear(const std::vector<std::vector<uint64_t>> &keys)
+{
+    PolTabs P;
+    P.keys = keys;
+    PolSlot empty{};
+    empty.key = POL_EMPTY;
+    empty.ctr = EMPTY;
+    uint32_t ctr = 0;
+    for (const auto &ks : keys) {
+        uint32_t ns = 8;
+        while (ns < 4 * ks.size())
+            ns <<= 1;
+        PolLoc loc;
+        loc.present = 1;
+        loc.base = (uint32_t)P.pol.size();
+        loc.mask = ns - 1;
+        P.pol.resize(P.pol.size() + ns, empty);
+        for (uint64_t k : ks) {
+            uint32_t s = pol_slot(pol_key_pre((uint32_t)k, (uint32_t)(k >> 32)), loc.mask);
+            while (P.pol[loc.base + s].key != POL_EMPTY)
+                s = (s + 1) & loc.mask;
+            P.pol[loc.base + s].key = k;
+            P.pol[loc.base + s].proxy_port = (uint16_t)(ctr * 7);
+            P.pol[loc.base + s].ctr = ctr++;
+        }
+        P.tabs.push_back(loc);
+    }
+    return P;
+}
+static int pol_direct_case(const char *name, const std::vector<std::vector<uint64_t>> &keys,
+                           uint32_t words, bool want_placed, std::mt19937 &gen)
+{
+    PolTabs P = pol_linear(keys);
+    const std::vector<PolSlot> before = P.pol;
+    std::vector<uint8_t> disp;
+    uint32_t maxd = 0;
+    const bool placed = pol_place_direct(&P.pol, P.tabs, words, &disp, &maxd);
+    int bad = placed != want_placed;
+    size_t nkeys = 0, d0 = 0;
+    if (!placed) {   // the linear tables stay as they were
+        bad |= !disp.empty() || memcmp(before.data(), P.pol.data(), sizeof(PolSlot) * before.size());
+    } else {
+        bad |= disp.size() != words;
+        uint32_t ctr = 0;
+        for (size_t t = 0; t < keys.size(); t++) {
+            const PolLoc &L = P.tabs[t];
+            const PolSlot *tab = P.pol.data() + L.base;
+            for (uint64_t k : keys[t]) {
+                const uint32_t s = pol_find_slot(tab, L.base, L.mask, k, disp);
+                bad |= s == EMPTY || tab[s].key != k || tab[s].ctr != ctr ||
+                       tab[s].proxy_port != (uint16_t)(ctr * 7);
+                ctr++;
+            }
+            size_t used = 0;
+            for (uint32_t s = 0; s <= L.mask; s++)
+                used += tab[s].key != POL_EMPTY;
+            bad |= used != keys[t].size();
+            nkeys += used;
+            for (int q = 0; q < 2000; q++) {   // absent keys (and, rarely, present ones)
+                const uint64_t k = ((uint64_t)(gen() & 0x01FFFFFFu) << 32) | (gen() & 0xFFFFu);
+                bool in = false;
+                for (uint64_t x : keys[t])
+                    in |= x == k;
+                bad |= (pol_find_slot(tab, L.base, L.mask, k, disp) != EMPTY) != in;
+            }
+        }
+        for (uint8_t d : disp)
+            d0 += d == 0;
+    }
+    printf("poldirect %-12s %zu tables, %zu keys, %u words: %s, max d %u, %zu words at d 0 -> %s\n",
+           name, keys.size(), nkeys, words, placed ? "placed" : "linear", maxd, d0,
+           bad ? "FAIL" : "ok");
+    return bad;
+}
+static uint64_t pol_rand_key(std::mt19937 &gen)
+{
+    // {identity, dport, proto, egress}: pad bits clear
+    return ((uint64_t)(gen() & 0x01FFFFFFu) << 32) | (gen() & 0xFFFFFFu);
+}
+static int pol_direct_tests()
+{
+    std::mt19937 gen(4242);   // (its own stream: the same cases alone and in the whole run)
+    int fail = 0;
+    auto distinct = [&](size_t n) {
+        std::map<uint64_t, int> seen;
+        std::vector<uint64_t> v;
+        while (v.size() < n) {
+            const uint64_t k = pol_rand_key(gen);
+            if (seen.emplace(k, 1).second)
+                v.push_back(k);
+        }
+        return v;
+    };
+    {   // random: tables of every size class, about two keys per word
+        std::vector<std::vector<uint64_t>> T;
+        for (size_t n : {1u, 2u, 3u, 5u, 16u, 17u, 100u, 700u, 2000u, 4000u, 9000u})
+            T.push_back(distinct(n));
+        fail |= pol_direct_case("random", T, 8192, true, gen);
+    }
+    {   // piled: 400 smallest tables (2 and 3 keys in 8 and 16 slots) behind 64
+        // words, 15 keys to a word (a step is one of four values modulo 8:
+        // two keys of one 8-slot table that share word, home slot and step
+        // would never part; this seed's 1000 keys hold no such pair); and
+        // one table whose keys share a home slot
+        std::vector<std::vector<uint64_t>> T;
+        for (int i = 0; i < 400; i++)
+            T.push_back(distinct(2 + i % 2));
+        fail |= pol_direct_case("piled-small", T, 64, true, gen);
+        std::vector<uint64_t> same;
+        while (same.size() < 12) {
+            const uint64_t k = pol_rand_key(gen);
+            if ((pol_key_pre((uint32_t)k, (uint32_t)(k >> 32)) & 63) == 5)
+                same.push_back(k);
+        }
+        fail |= pol_direct_case("piled-home", {same}, 64, true, gen);
+    }
+    {   // equal pre: lo' * K ^ hi' = lo * K ^ hi — no displacement separates them
+        const uint32_t K = 0x9E3779B1u, lo = 1234, hi = 0x00060050u;
+        uint32_t lo2 = 1;
+        while (((lo2 * K) ^ (lo * K) ^ hi) >> 25)
+            lo2++;
+        const uint32_t hi2 = (lo2 * K) ^ (lo * K) ^ hi;
+        std::vector<uint64_t> v = distinct(20);
+        v.push_back((uint64_t)hi << 32 | lo);
+        v.push_back((uint64_t)hi2 << 32 | lo2);
+        fail |= pol_key_pre(lo, hi) != pol_key_pre(lo2, hi2) || (lo == lo2 && hi == hi2);
+        fail |= pol_direct_case("equal-pre", {v}, 64, false, gen);
+    }
+    {   // hundreds of keys to a word: no displacement within a byte
+        fail |= pol_direct_case("crowded", {distinct(40000)}, 64, false, gen);
+    }
+    return fail;
+}
+// known answers of pol_slot_direct: `pd pol_slot_direct <pre> <d> <mask> <slot>`
+static void pol_direct_kats()
+{
+    const uint32_t V[] = {0u, 0xFFFFFFFFu, 1u, 0x0100000Au, 0x9E3779B9u, 0x80000000u, 0x1010u,
+                          0x00070007u};
+    for (uint32_t pre : V)
+        for (uint32_t d : {0u, 1u, 2u, 7u, 19u, 255u})
+            for (uint32_t m : {7u, 63u, 511u, 0xFFFFu, 0xFFFFFu})
+                printf("pd pol_slot_direct %x %x %x %x\n", pre, d, m, pol_slot_direct(pre, d, m));
+}
+
 int main(int argc, char **argv)
 {
+    if (argc > 1 && !strcmp(argv[1], "poldirect")) {   // the direct policy placement alone
+        pol_direct_kats();
+        return pol_direct_tests();
+    }
     if (argc > 2 && !strcmp(argv[1], "kat") && !strcmp(argv[2], "selfcut")) {
         selfcut_kats();   // the cut rule's known answers alone
         return 0;
@@ -820,6 +979,7 @@ int main(int argc, char **argv)
     fail |= map_fuzz(gen);
     fail |= lpm4_tests(gen);
     fail |= hist_slot_tests(gen);
+    fail |= pol_direct_tests();
     fail |= ReplayCase<false>().run();
     fail |= ReplayCase<true>().run();
     return fail;

@@ -295,7 +295,8 @@ class Datapath:
 
     def set_option(self, option, value):
         """cfc_set_option: L.OPT_LPM4 (ipcache layout, next commit),
-        L.OPT_LPM4_DIR_BITS (its directory width, next commit) or
+        L.OPT_LPM4_DIR_BITS (its directory width, next commit),
+        L.OPT_POL_PLACEMENT (policy key placement, next commit) or
         L.OPT_TIMING (per-call kernel events)."""
         L.check(self.L.cfc_set_option(self.h, option, value), "set option")
 
@@ -584,6 +585,14 @@ class Datapath:
         L.check(self.L.cfc_lpm4_dir_stats(self.h, st, ctypes.byref(auto)), "lpm4 dir stats")
         return ({16 + i: {f: getattr(st[i], f) for f, _ in L.Lpm4DirStat._fields_}
                  for i in range(3)}, auto.value)
+
+    def pol_placement(self):
+        """cfc_pol_placement: how the current epoch placed the policy keys
+        -> (L.POL_PLACEMENT_LINEAR or _DIRECT, the largest displacement)"""
+        p, d = ctypes.c_int(0), ctypes.c_int(0)
+        L.check(self.L.cfc_pol_placement(self.h, ctypes.byref(p), ctypes.byref(d)),
+                "pol placement")
+        return p.value, d.value
 
 
 def host_only():

@@ -193,7 +193,16 @@ int cfc_commit(cfc_ctx *ctx, void *stream);
  * closest to expiry that the batch's lookups did not hit are deleted first
  * (as a GC would; the reference's LRU hash evicts its least recently used
  * entries instead, in an order the kernel's per-CPU lists decide); 0 = such
- * a batch takes the host walk, whose maps evict in LRU order. */
+ * a batch takes the host walk, whose maps evict in LRU order.
+ * CFC_OPT_POL_PLACEMENT: how the policy keys are placed in the endpoints'
+ * device tables, applied at the next commit.  DIRECT places every key
+ * collision-free (hash-and-displace, one displacement byte per word of the
+ * policy Bloom filter), so a lookup is decided by one probe; LINEAR is open
+ * addressing with linear probing.  AUTO (default) takes DIRECT when a
+ * displacement exists for every key and the displacement bytes fit the
+ * classify kernels' on-chip image, else LINEAR; forced DIRECT fails the
+ * commit with -ENOSPC instead.  cfc_pol_placement reports what the epoch
+ * took.  Lookups give the same result under both. */
 #define CFC_OPT_LPM4 1
 #define CFC_LPM4_AUTO 0
 #define CFC_LPM4_DIR24_8 1
@@ -204,6 +213,10 @@ int cfc_commit(cfc_ctx *ctx, void *stream);
 #define CFC_CT_APPLY_HOST 1
 #define CFC_OPT_CT_EVICT 4
 #define CFC_OPT_LPM4_DIR_BITS 5
+#define CFC_OPT_POL_PLACEMENT 6
+#define CFC_POL_PLACEMENT_AUTO 0
+#define CFC_POL_PLACEMENT_LINEAR 1
+#define CFC_POL_PLACEMENT_DIRECT 2
 int cfc_set_option(cfc_ctx *ctx, int option, int64_t value);
 
 /* ---------------------------------------------------------------- datapath */
@@ -809,6 +822,12 @@ typedef struct {
     uint64_t bytes;
 } cfc_lpm4_dir_stat;
 int cfc_lpm4_dir_stats(cfc_ctx *ctx, cfc_lpm4_dir_stat st[3], int *auto_bits);
+
+/* The policy placement of the current epoch (CFC_OPT_POL_PLACEMENT):
+ * *placement = CFC_POL_PLACEMENT_LINEAR or _DIRECT, *max_disp = the largest
+ * displacement byte of a direct placement (0 under linear).  Either pointer
+ * may be null.  -ENOENT before the first commit. */
+int cfc_pol_placement(cfc_ctx *ctx, int *placement, int *max_disp);
 
 #ifdef __cplusplus
 }
