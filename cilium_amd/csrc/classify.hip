@@ -2030,8 +2030,8 @@ int launch_classify_v4(const DevTables &T, const cfc_hdr_v4 &in,
         // packet's daddr / L4 word from it and the tuple it left
         uint32_t *a = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(ws) + w.lb);
         const uint64_t st = ctr_stride(in.n);
-        LbArgs A{in.saddr, in.daddr, in.ports, in.meta, in.hash, in.n, E.ct_owner,
-                 a, a + st, a + 2 * st, a + 3 * st, a + 4 * st, a + 5 * st, E.svo};
+        LbArgs A{in.saddr, in.daddr, in.ports, in.meta, in.hash, in.n, E.lxc_id,
+                 E.ct_owner, a, a + st, a + 2 * st, a + 3 * st, a + 4 * st, a + 5 * st, E.svo};
         if (int rc = launch_lb4_egress(T, A, s))
             return rc;
         li = LbIn{A.tda, A.tpt, A.psa, A.fl};

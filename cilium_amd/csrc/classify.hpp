@@ -542,7 +542,7 @@ int ct_gc_log(const CtGcArgs &A, const CtLog6 *in, uint32_t n, CtLog6 *out, hipS
 struct LbArgs {
     const uint32_t *sa, *da, *pt, *mt, *hash;   // the batch (hash may be null)
     uint64_t n;
-    uint32_t ct_owner;                            // the sender's CT maps
+    uint32_t lxc_id, ct_owner;                    // the sending endpoint, its CT maps
     uint32_t *tda, *tpt, *psa, *pda, *ppt, *fl;   // per header (lb.hip)
     const uint32_t *svo;   // per header the CT_SERVICE entry in packet order, or null
 };

@@ -15,7 +15,7 @@
 //             and the caller see it: translated, reverse-NATed
 //   fl        LBF_DROP (DROP_NO_SERVICE), LBF_SVC, LBF_LOOP, and the
 //             backend's rev_nat_index in bits 16-31
-#include "kern_common.hpp"
+#include "ctops.hpp"
 
 namespace cfc {
 
@@ -34,7 +34,11 @@ __global__ __launch_bounds__(256) void k_lb4_egress(DevTables T, LbArgs A)
     // protocol skips the service step (DROP_UNKNOWN_L4 -> skip_service_lookup)
     uint32_t kd = l4 ? pt >> 16 : 0u;
     uint4 a, b;
-    if (T.lb4 && (l4 || proto == 1) && lb4_service(T, da, kd, 0, a, b)) {
+    // (a source that is not the sending endpoint's is dropped before
+    // lb4_local and before the sender's ct_lookup4, bpf_lxc.c:464-469: the
+    // packet leaves as it came; looked up only where a rewrite is due)
+    if (T.lb4 && (l4 || proto == 1) && lb4_service(T, da, kd, 0, a, b) &&
+        lb4_src_ok(T, sa, A.lxc_id)) {
         const uint32_t hash = A.hash ? A.hash[i] : flow_hash4(sa, da, pt, proto);
         // lb4_local: ct_lookup4(CT_SERVICE) — the tuple as loaded, one probe
         uint32_t slave, loop = 0;
@@ -81,7 +85,7 @@ __global__ __launch_bounds__(256) void k_lb4_egress(DevTables T, LbArgs A)
     if (!(fl & LBF_DROP) && T.ct4_lb && (l4 || proto == 1)) {
         const CtProbe k = ct_probe<false>(proto, tpt, CT_EGRESS, A.ct_owner);
         const uint32_t slot = ct4_find(T, tda, sa, k.z1, k.w1);
-        if (slot != NONE)
+        if (slot != NONE && lb4_src_ok(T, sa, A.lxc_id))
             lb4_rev_nat(T, ld16(T.ct4_lb + slot), proto, psa, pda, ppt);
     }
     A.tda[i] = tda;

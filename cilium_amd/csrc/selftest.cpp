@@ -309,6 +309,49 @@ static void selfcut_kats()
     }
 }
 
+// `kat svchash`: LCG-drawn CT key words (d, s, z, w) of both families with
+// their layout.h fingerprint (ct_hash4 / ct_hash6: what svcorder.hip groups
+// its list by) and home slot (ct_home4 / ct_home6: what ctapply.hip k_cta_svc
+// groups by), for the restatement in tests/svc_edges.py.  Lines `svchash 4
+// <d> <s> <z> <w> <hash> <home>` and `svchash 6 <d0..d3> <s0..s3> <z> <w>
+// <hash> <home>`, hex.  Every fourth row repeats the one before it with the
+// two addresses and the two ports exchanged and the direction bit of w
+// flipped: the same home, another fingerprint.
+static void svchash_kats()
+{
+    uint32_t s = 0x51c0a7e5u;
+    auto lcg = [&s]() -> uint32_t {
+        s = s * 1664525u + 1013904223u;
+        return s >> 8;
+    };
+    auto word = [&lcg]() -> uint32_t { return lcg() << 16 ^ lcg(); };
+    const uint32_t PROTO[] = {6, 17, 1, 58};
+    uint32_t d[4] = {0, 0, 0, 0}, a[4] = {0, 0, 0, 0}, z = 0, w = 0;
+    for (int v6 = 0; v6 < 2; v6++)
+        for (int i = 0; i < 200; i++) {
+            if (i % 4 == 3) {
+                for (int k = 0; k < 4; k++)
+                    std::swap(d[k], a[k]);
+                z = z >> 16 | z << 16;
+                w ^= 0x100u;
+            } else {
+                for (int k = 0; k < 4; k++) {
+                    d[k] = word();
+                    a[k] = word();
+                }
+                z = i % 5 == 0 ? word() & 0xFFFFu : word();
+                w = ct_word(PROTO[lcg() % 4], lcg() % 8,
+                            lcg() % 2 ? ct_owner_word(lcg() & 0xFFFFu, true) : 0u);
+            }
+            if (v6)
+                printf("svchash 6 %x %x %x %x %x %x %x %x %x %x %x %x\n", d[0], d[1], d[2], d[3],
+                       a[0], a[1], a[2], a[3], z, w, ct_hash6(d, a, z, w), ct_home6(d, a, z, w));
+            else
+                printf("svchash 4 %x %x %x %x %x %x\n", d[0], a[0], z, w,
+                       ct_hash4(d[0], a[0], z, w), ct_home4(d[0], a[0], z, w));
+        }
+}
+
 static uint32_t brute(const std::vector<Pfx6> &pfx, const uint32_t w[4])
 {
     int best = -1;
@@ -919,6 +962,10 @@ int main(int argc, char **argv)
     }
     if (argc > 2 && !strcmp(argv[1], "kat") && !strcmp(argv[2], "selfcut")) {
         selfcut_kats();   // the cut rule's known answers alone
+        return 0;
+    }
+    if (argc > 2 && !strcmp(argv[1], "kat") && !strcmp(argv[2], "svchash")) {
+        svchash_kats();   // the CT key fingerprints and home slots alone
         return 0;
     }
     hash_kats();
