@@ -14,6 +14,9 @@ CFC_DEVICE_NONE = -1
 MODE_INGRESS, MODE_EGRESS, MODE_XDP, MODE_FULL = 0, 1, 2, 3
 HF_FRAG, HF_TCP_CLOSE, HF_EXTHDR = 0x100, 0x200, 0x400
 DROP_PREFILTER, VERDICT_PUNT = -1, -2
+# a header reverse_proxy translated (cfc_classify_from_host_*): its mark
+MARK_TRANSLATED = 0x1000
+MARK_HIT = 0xA00 | MARK_TRANSLATED
 OPT_LPM4, OPT_TIMING, OPT_CT_APPLY, OPT_CT_EVICT = 1, 2, 3, 4
 OPT_LPM4_DIR_BITS = 5
 OPT_POL_PLACEMENT = 6
@@ -38,6 +41,7 @@ EXPORTS = (
     "cfc_proxy_entries_v4", "cfc_proxy_entries_v6",
     "cfc_proxy_apply_v4", "cfc_proxy_apply_v6", "cfc_lpm4_dir_stats",
     "cfc_pol_placement",
+    "cfc_classify_from_host_v4", "cfc_classify_from_host_v6",
 )
 # CT byte (cfc_out.ct): per stage (bits 0-3, then 4-7 for the destination's
 # ingress lookup after egress local delivery)
@@ -91,6 +95,13 @@ class Out(ctypes.Structure):
                 ("action", ctypes.c_void_p), ("ct", ctypes.c_void_p),
                 ("notify", ctypes.c_void_p), ("pkt_saddr", ctypes.c_void_p),
                 ("pkt_daddr", ctypes.c_void_p), ("pkt_ports", ctypes.c_void_p)]
+
+
+class RevproxyCols(ctypes.Structure):
+    """cfc_revproxy_cols (cfc_classify_from_host_v4/v6)"""
+    _fields_ = [("saddr", ctypes.c_void_p), ("ports", ctypes.c_void_p),
+                ("mark", ctypes.c_void_p), ("identity", ctypes.c_void_p),
+                ("hits", ctypes.c_void_p)]
 
 
 class Stats(ctypes.Structure):
@@ -221,6 +232,13 @@ def lib():
         L.cfc_lpm4_dir_stats.argtypes = [vp, ctypes.POINTER(Lpm4DirStat), pint]
     if hasattr(L, "cfc_pol_placement"):
         L.cfc_pol_placement.argtypes = [vp, pint, pint]
+    if hasattr(L, "cfc_classify_from_host_v4"):
+        L.cfc_classify_from_host_v4.argtypes = [vp, ctypes.POINTER(HdrV4),
+                                                ctypes.POINTER(RevproxyCols),
+                                                ctypes.POINTER(Out), vp]
+        L.cfc_classify_from_host_v6.argtypes = [vp, ctypes.POINTER(HdrV6),
+                                                ctypes.POINTER(RevproxyCols),
+                                                ctypes.POINTER(Out), vp]
     L.cfc_strerror.argtypes = [i32]
     L.cfc_strerror.restype = ctypes.c_char_p
     _lib = L

@@ -85,6 +85,12 @@ struct GLb {           // load balancing: services, reverse NAT
     uint32_t lb4_mask = 0, n_lb4 = 0, lb6_mask = 0, n_lb6 = 0;
     uint64_t bytes = 0;
 };
+struct GRp {           // the proxy maps as reverse_proxy looks them up (layout.h RevTables)
+    DevBuf rp4, rp4_val, rp6, rp6_val;
+    RevTables R{};
+    uint32_t n_rp4 = 0, n_rp6 = 0;
+    uint64_t bytes = 0;
+};
 struct GCt {           // conntrack
     CtTab<Ct4Slot> t4;   // per family (ctmirror.hpp): the table, its host mirror
     CtTab<Ct6Slot> t6;
@@ -118,6 +124,7 @@ struct Epoch {
     std::shared_ptr<GEp> ep;
     std::shared_ptr<GCt> ct;
     std::shared_ptr<GLb> lb;
+    std::shared_ptr<GRp> rp;
     DevTables T{};
     cfc_stats st{};
 };
@@ -147,7 +154,7 @@ struct cfc_ctx {
 
     std::shared_ptr<Epoch> epoch;
     uint64_t epoch_seq = 0;
-    uint64_t built_sig[6] = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull};   // per group
+    uint64_t built_sig[7] = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull};   // per group
     uint32_t id_cover = 1;   // identity histogram ranges (reserved + ipcache)
     std::vector<Retired> retired;
     std::vector<hipStream_t> streams;   // streams launched on since the last swap
@@ -316,10 +323,10 @@ void order_after_launches(cfc_ctx *c, hipStream_t s)
 
 // Signatures of the maps behind each table group, bit g of GROUP_*
 // (0 ipcache v4, 1 prefilter, 2 endpoints + policy, 3 CT, 4 ipcache v6,
-// 5 load balancing).
+// 5 load balancing, 6 the proxy maps).
 // Structural changes (inserts, deletes) count; a value overwritten in place
 // does not where a commit can patch it (ipcache v6 labels, policy entries).
-constexpr int NGROUPS = 6;
+constexpr int NGROUPS = 7;
 void group_sigs(cfc_ctx *c, uint64_t sig[NGROUPS])
 {
     for (int g = 0; g < NGROUPS; g++)
@@ -357,6 +364,9 @@ void group_sigs(cfc_ctx *c, uint64_t sig[NGROUPS])
             // the CT table carries each entry's LB state while a load
             // balancer is configured
             mix(3, m->kv.empty() ? 0 : 1);
+            break;
+        case ROLE_PROXY4: case ROLE_PROXY6:
+            mix(6, id); mix(6, m->gen);
             break;
         default:
             break;
@@ -848,6 +858,29 @@ std::shared_ptr<GLb> build_lbg(const HostImage &img, hipStream_t s, int *rc)
     return g;
 }
 
+std::shared_ptr<GRp> build_rpg(const HostImage &img, hipStream_t s, int *rc)
+{
+    auto g = std::make_shared<GRp>();
+    if (img.rp_too_big) {
+        *rc = -E2BIG;
+        return nullptr;
+    }
+    if ((*rc = upload_vec(g->rp4, img.rp4, s)) || (*rc = upload_vec(g->rp4_val, img.rp4_val, s)) ||
+        (*rc = upload_vec(g->rp6, img.rp6, s)) || (*rc = upload_vec(g->rp6_val, img.rp6_val, s)))
+        return nullptr;
+    g->n_rp4 = img.n_rp4;
+    g->n_rp6 = img.n_rp6;
+    g->R.rp4 = img.n_rp4 ? (const uint4 *)g->rp4.p : nullptr;
+    g->R.rp4_val = (const uint32_t *)g->rp4_val.p;
+    g->R.rp4_mask = img.rp4_mask;
+    g->R.rp6 = img.n_rp6 ? (const uint4 *)g->rp6.p : nullptr;
+    g->R.rp6_val = (const uint4 *)g->rp6_val.p;
+    g->R.rp6_mask = img.rp6_mask;
+    g->bytes = 16ull * img.rp4.size() + 4ull * img.rp4_val.size() + 16ull * img.rp6.size() +
+               16ull * img.rp6_val.size();
+    return g;
+}
+
 std::shared_ptr<GCt> build_ctg(HostImage &img, const std::vector<Map *> &ms, hipStream_t s,
                                int *rc)
 {
@@ -970,7 +1003,7 @@ void assemble(Epoch &E)
     cfc_stats &st = E.st;
     st = cfc_stats{};
     st.epoch = E.id;
-    st.device_bytes = I.bytes + I6.bytes + P.bytes + D.bytes + C.bytes + B.bytes;
+    st.device_bytes = I.bytes + I6.bytes + P.bytes + D.bytes + C.bytes + B.bytes + E.rp->bytes;
     st.ipcache_v4_prefixes = I.n_prefix4;
     st.lpm4_tbl8_groups = I.tbl8_groups;
     st.policy_entries = T.n_ctr;
@@ -1242,11 +1275,17 @@ bool patch_ct(cfc_ctx *c, hipStream_t s)
     return true;
 }
 
-int commit_locked(cfc_ctx *c, hipStream_t s)
+// proxy: an explicit cfc_commit — the only commit that re-flattens the proxy
+// maps' table once an epoch exists (cfc.h "From-host batches": the reverse
+// lookups see the maps as of the last cfc_commit, and a classify's
+// auto-commit behind every cfc_proxy_apply_* would rebuild it per batch)
+int commit_locked(cfc_ctx *c, hipStream_t s, bool proxy = false)
 {
     reap_retired(c);
     uint64_t sig[NGROUPS];
     group_sigs(c, sig);
+    if (c->epoch && !proxy)
+        sig[6] = c->built_sig[6];
     unsigned groups = 0;
     bool touched = false;
     for (int g = 0; g < NGROUPS; g++)
@@ -1303,6 +1342,8 @@ int commit_locked(cfc_ctx *c, hipStream_t s)
         E->ct = (groups & GROUP_CT) ? build_ctg(img, ms, s, &rc) : c->epoch->ct;
     if (!rc)
         E->lb = (groups & GROUP_LB) ? build_lbg(img, s, &rc) : c->epoch->lb;
+    if (!rc)
+        E->rp = (groups & GROUP_PROXY) ? build_rpg(img, s, &rc) : c->epoch->rp;
     if (rc)
         return rc;
     assemble(*E);
@@ -1814,7 +1855,7 @@ int cfc_commit(cfc_ctx *c, void *stream)
     if (c->device == CFC_DEVICE_NONE)
         return -ENODEV;
     (void)hipSetDevice(c->device);
-    return commit_locked(c, (hipStream_t)stream);
+    return commit_locked(c, (hipStream_t)stream, true);
 }
 
 }  // extern "C"
@@ -1974,6 +2015,27 @@ int nat_hop(cfc_ctx *c, const DevTables &T, const EgressArgs &ea, const Hdr &in,
         r.family = 0;   // (no apply follows)
     return rc;
 }
+
+// the family's classify launch as classify_one calls it; tr_id: a from-host
+// batch's identity column (classify_from_host), else null
+struct Launch4 {
+    const uint32_t *tr_id = nullptr;
+    int operator()(const DevTables &T, const cfc_hdr_v4 &in, const cfc_out &out, int mode,
+                   const EgressArgs &E, uint64_t *ctr, uint32_t *ws, int cus, hipStream_t s,
+                   const LaunchTiming *tm) const
+    {
+        return launch_classify_v4(T, in, out, mode, E, ctr, ws, cus, s, tm, tr_id);
+    }
+};
+struct Launch6 {
+    const uint32_t *tr_id = nullptr;
+    int operator()(const DevTables &T, const cfc_hdr_v6 &in, const cfc_out &out, int mode,
+                   const EgressArgs &E, uint64_t *ctr, uint32_t *ws, int cus, hipStream_t s,
+                   const LaunchTiming *tm) const
+    {
+        return launch_classify_v6(T, in, out, mode, E, ctr, ws, cus, s, tm, tr_id);
+    }
+};
 
 // cfc_classify_v4 / _v6: validation, auto-commit, workspace, launch
 template <class Hdr, class Launch>
@@ -2406,13 +2468,96 @@ extern "C" {
 int cfc_classify_v4(cfc_ctx *c, const cfc_hdr_v4 *in, const cfc_out *out,
                     int mode, uint16_t ep_lxc, void *stream)
 {
-    return classify(c, in, out, mode, ep_lxc, stream, launch_classify_v4);
+    return classify(c, in, out, mode, ep_lxc, stream, Launch4{});
 }
 
 int cfc_classify_v6(cfc_ctx *c, const cfc_hdr_v6 *in, const cfc_out *out,
                     int mode, uint16_t ep_lxc, void *stream)
 {
-    return classify(c, in, out, mode, ep_lxc, stream, launch_classify_v6);
+    return classify(c, in, out, mode, ep_lxc, stream, Launch6{});
+}
+
+}  // extern "C"
+
+namespace {
+
+// cfc_classify_from_host_v4 / _v6: the reverse-proxy pass over the batch
+// (revproxy.hip; with no table for the family: copies), then the INGRESS
+// classification of the translated batch, registered as any other launch
+template <class Hdr, class Launch>
+int classify_from_host(cfc_ctx *c, const Hdr *in, const cfc_revproxy_cols *tr,
+                       const cfc_out *out, void *stream)
+{
+    constexpr bool V6 = std::is_same<Hdr, cfc_hdr_v6>::value;
+    if (!c || !in || !tr || !out || !out->verdict || !out->identity)
+        return -EINVAL;
+    if (!tr->saddr || !tr->ports || !tr->mark || !tr->identity)
+        return -EINVAL;
+    if (in->n && (!in->saddr || !in->daddr || !in->ports || !in->meta))
+        return -EINVAL;
+    if (V6 && (((uintptr_t)in->saddr | (uintptr_t)in->daddr | (uintptr_t)tr->saddr) & 15))
+        return -EINVAL;   // 16-byte address rows
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    if (c->device == CFC_DEVICE_NONE)
+        return -ENODEV;
+    (void)hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    int rc = commit_locked(c, s);
+    if (rc)
+        return rc;
+    const Epoch &E = *c->epoch;
+    const RevTables &R = E.rp->R;
+    const bool table = V6 ? R.rp6 != nullptr : R.rp4 != nullptr;
+    const uint64_t n = in->n;
+    const size_t ab = V6 ? 16 : 4;
+    // (the pass adds into the count: zeroed before it; without a pass the
+    // zeroing goes behind the classify launch, off the call's critical path)
+    if (tr->hits && table && n && hipMemsetAsync(tr->hits, 0, 8, s) != hipSuccess)
+        return -EIO;
+    if (table && n) {
+        RevArgs A{in->saddr, in->daddr, in->ports, in->meta, in->mark, tr->saddr,
+                  tr->ports, tr->mark, tr->identity, (unsigned long long *)tr->hits, n};
+        if ((rc = launch_revproxy(E.T, R, A, V6, c->num_cus, s)))
+            return rc;
+        note_stream(c, s);
+    } else if (n) {   // nothing can hit: the columns that do not alias, copied
+        if (tr->saddr != (const void *)in->saddr &&
+            hipMemcpyAsync(tr->saddr, in->saddr, ab * n, hipMemcpyDeviceToDevice, s) != hipSuccess)
+            return -EIO;
+        if (tr->ports != in->ports &&
+            hipMemcpyAsync(tr->ports, in->ports, 4 * n, hipMemcpyDeviceToDevice, s) != hipSuccess)
+            return -EIO;
+        if (tr->mark != in->mark &&
+            (in->mark ? hipMemcpyAsync(tr->mark, in->mark, 4 * n, hipMemcpyDeviceToDevice, s)
+                      : hipMemsetAsync(tr->mark, 0, 4 * n, s)) != hipSuccess)
+            return -EIO;
+    }
+    Hdr th = *in;
+    th.saddr = (decltype(th.saddr))tr->saddr;
+    th.ports = tr->ports;
+    th.mark = tr->mark;
+    // (no table: no row can carry the bit — the plain launch, as cfc_classify_*)
+    rc = classify(c, &th, out, CFC_MODE_INGRESS, 0, stream,
+                  Launch{table ? tr->identity : nullptr});
+    if (!rc && tr->hits && !(table && n) && hipMemsetAsync(tr->hits, 0, 8, s) != hipSuccess)
+        rc = -EIO;
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cfc_classify_from_host_v4(cfc_ctx *c, const cfc_hdr_v4 *in, const cfc_revproxy_cols *tr,
+                              const cfc_out *out, void *stream)
+{
+    return classify_from_host<cfc_hdr_v4, Launch4>(c, in, tr, out, stream);
+}
+
+int cfc_classify_from_host_v6(cfc_ctx *c, const cfc_hdr_v6 *in, const cfc_revproxy_cols *tr,
+                              const cfc_out *out, void *stream)
+{
+    return classify_from_host<cfc_hdr_v6, Launch6>(c, in, tr, out, stream);
 }
 
 }  // extern "C"

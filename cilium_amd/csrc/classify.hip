@@ -261,9 +261,12 @@ __device__ __forceinline__ void r2_issue(const DevTables &T, const Lds &S,
 
 // round 3: second-level LPM, endpoint resolution, prefilter verdict,
 // identity, and the first policy key that may exist
-template <int MODE, bool CT, bool LB>
+// TR (ingress, behind the reverse-proxy pass): a header whose mark carries
+// CFC_MARK_TRANSLATED takes its source identity from E.tr_id[i] as it stands
+template <int MODE, bool CT, bool LB, bool TR>
 __device__ __forceinline__ void r3_identity(const DevTables &T, const Lds &S,
-                                            const EgressArgs &E, Hdr &h)
+                                            const EgressArgs &E, Hdr &h, const uint32_t *tr_id,
+                                            uint32_t i)
 {
     constexpr bool XDP = MODE == CFC_MODE_XDP || MODE == CFC_MODE_FULL;
     constexpr bool EGR = MODE == CFC_MODE_EGRESS;
@@ -340,6 +343,11 @@ __device__ __forceinline__ void r3_identity(const DevTables &T, const Lds &S,
         const bool ovr = (id < HEALTH_ID) & (h.e24 != 0u) & (h.e24 != CLUSTER_ID) &
                          (h.e24 != HOST_ID);
         h.ident = ovr ? h.e24 : id;
+        // reverse_proxy rewrote the source (bpf_netdev.c:400-416): the
+        // identity is the one handle_ipv4 derived before it, from the
+        // original source (revproxy.hip); the mark's 0xA00 is skip-proxy
+        if (TR && (h.mk & CFC_MARK_TRANSLATED))
+            h.ident = tr_id[i];
         // the destination endpoint's program: missed tail call, unknown
         // protocol, or its policy
         const bool ep = local & !(h.rec.w & LXC_HOST);
@@ -695,10 +703,14 @@ __device__ __forceinline__ void acc_publish(const unsigned long long *s_met,
 // SGPRs and exec-mask pairs they would hold for the whole loop.  FAST is the
 // width of the LPM directory (16, 17 or 18, layout.h; 0: the generic
 // kernel), so its shift is a constant too and costs no SGPR.
-template <int MODE, int U, bool CT, bool NT, bool OPT, bool LB, int FAST>
+// TR: launched by cfc_classify_from_host_v4 with a proxy-map table: bit 12 of
+// a header's mark (CFC_MARK_TRANSLATED) is the reverse-proxy pass's, and
+// tr_id holds such a header's source identity.  Every other launch ignores
+// the bit.
+template <int MODE, int U, bool CT, bool NT, bool OPT, bool LB, int FAST, bool TR = false>
 __global__ __launch_bounds__(BLOCK, WAVES_PER_SIMD) void k_classify_v4(
     DevTables T, LdsPlan L, cfc_hdr_v4 in, cfc_out out, EgressArgs E,
-    CountArgs C, uint64_t per_block, LbIn LI)
+    CountArgs C, uint64_t per_block, LbIn LI, const uint32_t *tr_id)
 {
     if (FAST) {
         T.tbl24 = T.tbl8 = T.pf_tbl24 = T.pf_tbl8 = nullptr;
@@ -784,6 +796,8 @@ __global__ __launch_bounds__(BLOCK, WAVES_PER_SIMD) void k_classify_v4(
         C.ctr2 += start;
     if (C.id)
         C.id += start;
+    if (TR)
+        tr_id += start;
     // the trip count is uniform across the workgroup (the metrics flush
     // needs whole waves)
     MetAcc<acc_n<MODE>()> acc;
@@ -803,7 +817,8 @@ __global__ __launch_bounds__(BLOCK, WAVES_PER_SIMD) void k_classify_v4(
             r2_issue<MODE>(T, S, h[u]);
 #pragma unroll
         for (int u = 0; u < U; u++)
-            r3_identity<MODE, CT, LB>(T, S, E, h[u]);
+            r3_identity<MODE, CT, LB, TR>(T, S, E, h[u], tr_id,
+                                          min(base + u * BLOCK + threadIdx.x, end - 1));
         // the next iteration's headers, behind this one's policy probe (the
         // last iteration re-reads the slice's last header)
         const uint32_t nb = base + BLOCK * U;
@@ -1797,7 +1812,7 @@ bool fast_shape(const DevTables &T, int mode, const LdsPlan &L)
 template <int MODE, bool CT, bool NT>
 void launch_mode_nt(const DevTables &T, const cfc_hdr_v4 &in, const cfc_out &out,
                     const EgressArgs &E, const CountArgs &C, uint32_t grid,
-                    uint64_t per_block, hipStream_t s, const LbIn *lb)
+                    uint64_t per_block, hipStream_t s, const LbIn *lb, const uint32_t *tr_id)
 {
     const LdsPlan L = lds_plan(T);
     const bool opt = in.mark || in.tcp_flags || out.action || (CT && out.ct);
@@ -1818,21 +1833,32 @@ void launch_mode_nt(const DevTables &T, const cfc_hdr_v4 &in, const cfc_out &out
         if (lb)
             kern = k_classify_v4<MODE, CFC_UNROLL, CT, NT, true, true, 0>;
     }
+    // behind the reverse-proxy pass (the mark column is always there: OPT);
+    // FAST stays with the launches without translation
+    if constexpr (MODE == CFC_MODE_INGRESS) {
+        if (tr_id) {
+            kern = k_classify_v4<MODE, CFC_UNROLL, CT, NT, true, false, 0, true>;
+            if constexpr (CT) {
+                if (lb)
+                    kern = k_classify_v4<MODE, CFC_UNROLL, CT, NT, true, true, 0, true>;
+            }
+        }
+    }
     set_lds_limit((const void *)kern, (int)LDS_PER_WG);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), L.bytes(), s, T, L, in,
-                       out, E, C, per_block, lb ? *lb : none);
+                       out, E, C, per_block, lb ? *lb : none, tr_id);
 }
 
 // the notify store is compiled in only when the caller asked for it
 template <int MODE, bool CT>
 void launch_mode(const DevTables &T, const cfc_hdr_v4 &in, const cfc_out &out,
                  const EgressArgs &E, const CountArgs &C, uint32_t grid,
-                 uint64_t per_block, hipStream_t s, const LbIn *lb)
+                 uint64_t per_block, hipStream_t s, const LbIn *lb, const uint32_t *tr_id)
 {
     if (out.notify)
-        launch_mode_nt<MODE, CT, true>(T, in, out, E, C, grid, per_block, s, lb);
+        launch_mode_nt<MODE, CT, true>(T, in, out, E, C, grid, per_block, s, lb, tr_id);
     else
-        launch_mode_nt<MODE, CT, false>(T, in, out, E, C, grid, per_block, s, lb);
+        launch_mode_nt<MODE, CT, false>(T, in, out, E, C, grid, per_block, s, lb, tr_id);
 }
 
 // histogram slices of an n-header batch with `slots` keys in all: one per
@@ -1998,7 +2024,7 @@ CountArgs count_args(uint32_t *ws, const WsLayout &w, const DevTables &T,
 int launch_classify_v4(const DevTables &T, const cfc_hdr_v4 &in,
                        const cfc_out &out, int mode, const EgressArgs &E,
                        uint64_t *g_ctr, uint32_t *ws, int num_cus, hipStream_t s,
-                       const LaunchTiming *tm)
+                       const LaunchTiming *tm, const uint32_t *tr_id)
 {
     if (in.n == 0)
         return 0;
@@ -2045,13 +2071,13 @@ int launch_classify_v4(const DevTables &T, const cfc_hdr_v4 &in,
     }
     const LbIn *lbp = lb ? &li : nullptr;
 #define CFC_LAUNCH(M)                                                        \
-    (ct ? launch_mode<M, true>(T, hin, out, E, C, grid, per_block, s, lbp)   \
-        : launch_mode<M, false>(T, hin, out, E, C, grid, per_block, s, lbp))
+    (ct ? launch_mode<M, true>(T, hin, out, E, C, grid, per_block, s, lbp, tr_id)   \
+        : launch_mode<M, false>(T, hin, out, E, C, grid, per_block, s, lbp, tr_id))
     switch (mode) {
     case CFC_MODE_INGRESS: CFC_LAUNCH(CFC_MODE_INGRESS); break;
     case CFC_MODE_EGRESS: CFC_LAUNCH(CFC_MODE_EGRESS); break;
     case CFC_MODE_XDP:
-        launch_mode<CFC_MODE_XDP, false>(T, hin, out, E, C, grid, per_block, s, nullptr);
+        launch_mode<CFC_MODE_XDP, false>(T, hin, out, E, C, grid, per_block, s, nullptr, nullptr);
         break;
     case CFC_MODE_FULL: CFC_LAUNCH(CFC_MODE_FULL); break;
     default: return -22;

@@ -618,15 +618,39 @@ int nat_scatter(const uint32_t *idx, uint32_t m, const cfc_out &sub, const cfc_o
 // (nat_scatter restores them after the hop's apply)
 int nat_pre(const uint32_t *idx, uint32_t m, const cfc_out &out, bool third, hipStream_t s);
 
+// ---- reverse_proxy / reverse_proxy6 of a from-host batch (revproxy.hip)
+// The pass over the headers: a header whose {daddr, L4 word, nexthdr} the
+// proxy map holds gets its source address and port rewritten, the mark
+// 0xA00 | CFC_MARK_TRANSLATED and its final source identity.  An output
+// column that is its input column is written on hit rows only, any other on
+// every row (a miss copies its input; a null mk is 0).  IPv6: sa / osa are
+// 16-byte rows.  hits (or null): += the hit rows, one atomic per workgroup.
+struct RevArgs {
+    const void *sa, *da;
+    const uint32_t *pt, *mt, *mk;   // mk may be null
+    void *osa;
+    uint32_t *opt, *omk, *oid;
+    unsigned long long *hits;
+    uint64_t n;
+};
+int launch_revproxy(const DevTables &T, const RevTables &R, const RevArgs &A, bool v6,
+                    int num_cus, hipStream_t s);
+
 // dst[i] += src[i] for n u64 (counter import)
 int launch_add_u64(uint64_t *dst, const uint64_t *src, uint64_t n,
                    hipStream_t stream);
 
 // g_ctr: the counter block (policy entries, then metrics, then identities)
+// tr_id (INGRESS, a from-host batch behind the reverse-proxy pass; only
+// cfc_classify_from_host_* passes it, else null): per header the final source
+// identity of the rows whose mark carries CFC_MARK_TRANSLATED — such a row
+// takes it as it stands (no ipcache override).  (Not a field of EgressArgs:
+// a wider EgressArgs moved the SGPR spills of the existing kernels.)
 int launch_classify_v4(const DevTables &T, const cfc_hdr_v4 &in,
                        const cfc_out &out, int mode, const EgressArgs &E,
                        uint64_t *g_ctr, uint32_t *workspace, int num_cus,
-                       hipStream_t stream, const LaunchTiming *timing = nullptr);
+                       hipStream_t stream, const LaunchTiming *timing = nullptr,
+                       const uint32_t *tr_id = nullptr);
 
 // The counter kernels over the per-header keys the classify kernel left in
 // the workspace (both families): policy entries, identities, CT accounting.
@@ -639,7 +663,8 @@ bool launch_counters(const DevTables &T, const uint32_t *meta, const uint8_t *tf
 int launch_classify_v6(const DevTables &T, const cfc_hdr_v6 &in,
                        const cfc_out &out, int mode, const EgressArgs &E,
                        uint64_t *g_ctr, uint32_t *workspace, int num_cus,
-                       hipStream_t stream, const LaunchTiming *timing = nullptr);
+                       hipStream_t stream, const LaunchTiming *timing = nullptr,
+                       const uint32_t *tr_id = nullptr);
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (device,
 // kernel), thread-safe

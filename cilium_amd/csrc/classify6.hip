@@ -83,60 +83,7 @@ __device__ __forceinline__ uint32_t mkey6(int reason, int dir)
     }
 }
 
-// ---- IPv6 LPM (layout.h Lpm6): the label of the longest prefix holding the
-// host-order address a (a matched label 0 shadows shorter prefixes, as the
-// reference's trie does), def_label when none
-// The first group's Bloom word is a separate step (lpm6_bloom0) so that the
-// first loads of independent lookups of one header go out together.
-// loff: the dword offset of the table's length list in LDS (LdsPlan6)
-__device__ __forceinline__ uint64_t lpm6_bloom0(const Lpm6 &P, uint32_t loff, uint4 a)
-{
-    if (!P.nlen)
-        return 0;
-    const uint32_t w[4] = {a.x, a.y, a.z, a.w};
-    return P.bloom[l6_group_hash(w, (lds_word(loff) >> 8) & 255) & P.bloom_mask];
-}
-__device__ __forceinline__ uint32_t lpm6_lookup(const Lpm6 &P, uint32_t loff, uint4 a,
-                                                uint64_t bw0)
-{
-    const uint32_t w[4] = {a.x, a.y, a.z, a.w};
-    uint64_t bw = bw0;
-    for (uint32_t j = 0; j < P.nlen; j++) {
-        const uint32_t e = lds_word(loff + j);   // uniform
-        const uint32_t len = e & 255;
-        if ((e & L6_GROUP_FIRST) && j)
-            bw = P.bloom[l6_group_hash(w, (e >> 8) & 255) & P.bloom_mask];
-        const uint32_t m0 = a.x & l6_word_mask(len, 0), m1 = a.y & l6_word_mask(len, 1),
-                       m2 = a.z & l6_word_mask(len, 2), m3 = a.w & l6_word_mask(len, 3);
-        const uint32_t h = l6_hash(m0, m1, m2, m3, len);
-        const uint64_t b = l6_bloom_bits(h);
-        if ((bw & b) != b)
-            continue;
-        if (len <= 64) {   // (uniform) one 16-byte load per probe: {w0, w1, label, len}
-            for (uint32_t s = h & P.mask64;; s = (s + 1) & P.mask64) {
-                const uint4 k = ld16(P.slots64 + s);
-                if (k.w == len && k.x == m0 && k.y == m1)
-                    return k.z;
-                if (!k.w)
-                    break;
-            }
-            continue;
-        }
-        for (uint32_t s = h & P.mask;; s = (s + 1) & P.mask) {
-            const uint4 k = ld16(&P.slots[s].w[0]);
-            const uint4 v = ld16(&P.slots[s].label);   // {label, len, 0, 0}
-            if (v.y == len && k.x == m0 && k.y == m1 && k.z == m2 && k.w == m3)
-                return v.x;
-            if (!v.y)
-                break;
-        }
-    }
-    return P.def_label;
-}
-__device__ __forceinline__ uint32_t lpm6_lookup(const Lpm6 &P, uint32_t loff, uint4 a)
-{
-    return lpm6_lookup(P, loff, a, lpm6_bloom0(P, loff, a));
-}
+// (the IPv6 LPM lookup, lpm6_lookup, is in kern_common.hpp: revproxy.hip shares it)
 
 // ---- endpoints: {pol_base, pol_mask, info, 0} of the slot holding the raw
 // address, zeros when it is not local
@@ -270,10 +217,14 @@ __device__ __forceinline__ bool lb6_egress(const DevTables &T, const EgressArgs 
 // LB: the launch has an IPv6 load balancer or wants the packet outputs —
 // the egress service step (lb6_local), reverse NAT of hits (lb6_rev_nat) and
 // ipv6_policy's daddr rewrite are followed, and cfc_out.pkt_* written
-template <int MODE, bool CT, bool NT, bool LB>
+// TR: launched by cfc_classify_from_host_v6 with a proxy-map table: bit 12 of
+// a header's mark (CFC_MARK_TRANSLATED) is the reverse-proxy pass's, and
+// tr_id holds such a header's source identity (every other launch ignores
+// the bit)
+template <int MODE, bool CT, bool NT, bool LB, bool TR = false>
 __global__ __launch_bounds__(BLOCK, WAVES_PER_SIMD) void k_classify_v6(
     DevTables T, LdsPlan6 L, cfc_hdr_v6 in, cfc_out out, EgressArgs E,
-    CountArgs C, uint64_t per_block)
+    CountArgs C, uint64_t per_block, const uint32_t *tr_id)
 {
     constexpr bool XDP = MODE == CFC_MODE_XDP || MODE == CFC_MODE_FULL;
     constexpr bool EGR = MODE == CFC_MODE_EGRESS;
@@ -397,6 +348,13 @@ __global__ __launch_bounds__(BLOCK, WAVES_PER_SIMD) void k_classify_v6(
                 const bool hop = E.nat_id != nullptr;
                 if (hop)
                     ident = E.nat_id[i];
+                // reverse_proxy6 rewrote the source (bpf_netdev.c:218-234):
+                // the identity is the one handle_ipv6 derived before it, from
+                // the original source (revproxy.hip); the mark's 0xA00 is
+                // skip-proxy
+                const bool trn = TR && (mk & CFC_MARK_TRANSLATED);
+                if (trn)
+                    ident = tr_id[i];
                 if (xd) {   // send_drop_notify_error: no identity recorded
                     act = TC_ACT_SHOT;
                     ver = xd;
@@ -408,7 +366,7 @@ __global__ __launch_bounds__(BLOCK, WAVES_PER_SIMD) void k_classify_v6(
                 } else {
                     // handle_ipv6 (:203-213): reserved identities take the
                     // ipcache's unless it says CLUSTER_ID
-                    if (ident < HEALTH_ID && !hop) {
+                    if (ident < HEALTH_ID && !hop && !trn) {
                         const uint32_t label = lpm6_lookup(T.ipc6, lo_ipc, sa, bwi);
                         if (label && label != CLUSTER_ID)
                             ident = label;
@@ -757,25 +715,30 @@ __global__ __launch_bounds__(BLOCK, WAVES_PER_SIMD) void k_classify_v6(
 template <int MODE, bool CT, bool NT>
 void launch_mode6_nt(const DevTables &T, const cfc_hdr_v6 &in, const cfc_out &out,
                      const EgressArgs &E, const CountArgs &C, uint32_t grid,
-                     uint64_t per_block, hipStream_t s)
+                     uint64_t per_block, hipStream_t s, const uint32_t *tr_id)
 {
     const LdsPlan6 L = lds_plan6(T);
     const bool lb = MODE != CFC_MODE_XDP && (T.lb6 || T.rnat6 || out.pkt_saddr);
     auto kern = lb ? k_classify_v6<MODE, CT, NT, true> : k_classify_v6<MODE, CT, NT, false>;
+    if constexpr (MODE == CFC_MODE_INGRESS) {   // behind the reverse-proxy pass
+        if (tr_id)
+            kern = lb ? k_classify_v6<MODE, CT, NT, true, true>
+                      : k_classify_v6<MODE, CT, NT, false, true>;
+    }
     set_lds_limit((const void *)kern, (int)LDS_PER_WG);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), L.bytes(), s, T, L, in,
-                       out, E, C, per_block);
+                       out, E, C, per_block, tr_id);
 }
 
 template <int MODE, bool CT>
 void launch_mode6(const DevTables &T, const cfc_hdr_v6 &in, const cfc_out &out,
                   const EgressArgs &E, const CountArgs &C, uint32_t grid,
-                  uint64_t per_block, hipStream_t s)
+                  uint64_t per_block, hipStream_t s, const uint32_t *tr_id)
 {
     if (out.notify)
-        launch_mode6_nt<MODE, CT, true>(T, in, out, E, C, grid, per_block, s);
+        launch_mode6_nt<MODE, CT, true>(T, in, out, E, C, grid, per_block, s, tr_id);
     else
-        launch_mode6_nt<MODE, CT, false>(T, in, out, E, C, grid, per_block, s);
+        launch_mode6_nt<MODE, CT, false>(T, in, out, E, C, grid, per_block, s, tr_id);
 }
 
 }  // namespace
@@ -783,7 +746,7 @@ void launch_mode6(const DevTables &T, const cfc_hdr_v6 &in, const cfc_out &out,
 int launch_classify_v6(const DevTables &T, const cfc_hdr_v6 &in,
                        const cfc_out &out, int mode, const EgressArgs &E,
                        uint64_t *g_ctr, uint32_t *ws, int num_cus, hipStream_t s,
-                       const LaunchTiming *tm)
+                       const LaunchTiming *tm, const uint32_t *tr_id)
 {
     if (in.n == 0)
         return 0;
@@ -809,12 +772,12 @@ int launch_classify_v6(const DevTables &T, const cfc_hdr_v6 &in,
     const WsLayout w = ws_layout(in.n, T, mode, ct);
     const CountArgs C = count_args(ws, w, T, g_ctr + 2ull * T.n_ctr, mode, ct);
 #define CFC_LAUNCH6(M)                                                         \
-    (ct ? launch_mode6<M, true>(T, in, out, E, C, grid, per_block, s)          \
-        : launch_mode6<M, false>(T, in, out, E, C, grid, per_block, s))
+    (ct ? launch_mode6<M, true>(T, in, out, E, C, grid, per_block, s, tr_id)   \
+        : launch_mode6<M, false>(T, in, out, E, C, grid, per_block, s, tr_id))
     switch (mode) {
     case CFC_MODE_INGRESS: CFC_LAUNCH6(CFC_MODE_INGRESS); break;
     case CFC_MODE_EGRESS: CFC_LAUNCH6(CFC_MODE_EGRESS); break;
-    case CFC_MODE_XDP: launch_mode6<CFC_MODE_XDP, false>(T, in, out, E, C, grid, per_block, s); break;
+    case CFC_MODE_XDP: launch_mode6<CFC_MODE_XDP, false>(T, in, out, E, C, grid, per_block, s, nullptr); break;
     case CFC_MODE_FULL: CFC_LAUNCH6(CFC_MODE_FULL); break;
     default: return -22;
     }

@@ -789,6 +789,118 @@ static void build_ct(const std::vector<const Map *> &cts, HostImage *img)
     }
 }
 
+// cilium_proxy4 / cilium_proxy6 -> the tables reverse_proxy / reverse_proxy6
+// probe (layout.h RevTables).  Key bytes 4-7 (dport, sport) are one word, as
+// the reference loads the packet's first L4 word into them; the pad byte of
+// a key is not compared (the datapath's keys have it 0, and so have the
+// entries ipv{4,6}_redirect_to_host_port writes: others are left out).
+void build_revproxy(const Map *p4, const Map *p6, HostImage *img)
+{
+    img->rp4.clear();
+    img->rp4_val.clear();
+    img->rp6.clear();
+    img->rp6_val.clear();
+    img->rp4_mask = img->rp6_mask = img->n_rp4 = img->n_rp6 = 0;
+    img->rp_too_big = false;
+    if (p4 && p4->ksz == 10 && p4->vsz == 16 && !p4->kv.empty()) {
+        const uint64_t ns64 = 2ull * p4->kv.size();
+        if (ns64 * 16 > RP_MAX_TABLE_BYTES / 4) {
+            img->rp_too_big = true;
+            return;
+        }
+        const uint32_t ns = pow2_at_least(ns64);
+        img->rp4.assign(ns, make_uint4(0, 0, 0, 0));
+        img->rp4_val.assign(ns, 0u);
+        img->rp4_mask = ns - 1;
+        for (const auto &kv : p4->kv) {
+            const uint8_t *k = (const uint8_t *)kv.first.data();
+            const uint8_t *v = (const uint8_t *)kv.second.val.data();
+            if (kv.first.size() < 10 || kv.second.val.size() < 16 || k[9] != 0)
+                continue;
+            uint32_t sa, pt, od;
+            uint16_t op;
+            memcpy(&sa, k, 4);
+            memcpy(&pt, k + 4, 4);
+            memcpy(&od, v, 4);
+            memcpy(&op, v + 4, 2);
+            uint32_t i = rp4_hash(sa, pt, k[8]) & img->rp4_mask;
+            while (img->rp4[i].z & RP_USED)
+                i = (i + 1) & img->rp4_mask;
+            img->rp4[i] = make_uint4(sa, pt, k[8] | RP_USED, od);
+            img->rp4_val[i] = op;
+            img->n_rp4++;
+        }
+        if (!img->n_rp4) {
+            img->rp4.clear();
+            img->rp4_val.clear();
+            img->rp4_mask = 0;
+        }
+    }
+    if (p6 && p6->ksz == 22 && p6->vsz == 28 && !p6->kv.empty()) {
+        const uint64_t ns64 = 2ull * p6->kv.size();
+        if (ns64 * 32 > RP_MAX_TABLE_BYTES / 4) {
+            img->rp_too_big = true;
+            return;
+        }
+        const uint32_t ns = pow2_at_least(ns64);
+        img->rp6.assign(2ull * ns, make_uint4(0, 0, 0, 0));
+        img->rp6_val.assign(ns, make_uint4(0, 0, 0, 0));
+        img->rp6_mask = ns - 1;
+        for (const auto &kv : p6->kv) {
+            const uint8_t *k = (const uint8_t *)kv.first.data();
+            const uint8_t *v = (const uint8_t *)kv.second.val.data();
+            if (kv.first.size() < 22 || kv.second.val.size() < 28 || k[21] != 0)
+                continue;
+            uint32_t a[4], pt, od[4];
+            uint16_t op;
+            memcpy(a, k, 16);
+            memcpy(&pt, k + 16, 4);
+            memcpy(od, v, 16);
+            memcpy(&op, v + 16, 2);
+            uint32_t i = rp6_hash(a[0], a[1], a[2], a[3], pt, k[20]) & img->rp6_mask;
+            while (img->rp6[2 * i + 1].y & RP_USED)
+                i = (i + 1) & img->rp6_mask;
+            img->rp6[2 * i] = make_uint4(a[0], a[1], a[2], a[3]);
+            img->rp6[2 * i + 1] = make_uint4(pt, k[20] | RP_USED, op, 0);
+            img->rp6_val[i] = make_uint4(od[0], od[1], od[2], od[3]);
+            img->n_rp6++;
+        }
+        if (!img->n_rp6) {
+            img->rp6.clear();
+            img->rp6_val.clear();
+            img->rp6_mask = 0;
+        }
+    }
+}
+
+int64_t rp4_find_slot(const HostImage &img, uint32_t saddr, uint32_t ports, uint32_t nexthdr)
+{
+    if (img.rp4.empty())
+        return -1;
+    for (uint32_t i = rp4_hash(saddr, ports, nexthdr) & img.rp4_mask;; i = (i + 1) & img.rp4_mask) {
+        const uint4 &k = img.rp4[i];
+        if (!(k.z & RP_USED))
+            return -1;
+        if (k.x == saddr && k.y == ports && k.z == (nexthdr | RP_USED))
+            return i;
+    }
+}
+
+int64_t rp6_find_slot(const HostImage &img, const uint32_t a[4], uint32_t ports, uint32_t nexthdr)
+{
+    if (img.rp6.empty())
+        return -1;
+    for (uint32_t i = rp6_hash(a[0], a[1], a[2], a[3], ports, nexthdr) & img.rp6_mask;;
+         i = (i + 1) & img.rp6_mask) {
+        const uint4 &k = img.rp6[2 * i], &w = img.rp6[2 * i + 1];
+        if (!(w.y & RP_USED))
+            return -1;
+        if (k.x == a[0] && k.y == a[1] && k.z == a[2] && k.w == a[3] && w.x == ports &&
+            w.y == (nexthdr | RP_USED))
+            return i;
+    }
+}
+
 void build_image(const std::vector<Map *> &maps, const BuildOpts &opt,
                  HostImage *img, unsigned groups)
 {
@@ -823,6 +935,16 @@ void build_image(const std::vector<Map *> &maps, const BuildOpts &opt,
     }
     if (groups & GROUP_CT)
         build_ct(cts, img);
+    if (groups & GROUP_PROXY) {
+        const Map *p4 = nullptr, *p6 = nullptr;
+        for (Map *m : maps) {
+            if (m->role == ROLE_PROXY4)
+                p4 = m;
+            else if (m->role == ROLE_PROXY6)
+                p6 = m;
+        }
+        build_revproxy(p4, p6, img);
+    }
     const Map *ipc = nullptr, *lxc = nullptr, *pf4fix = nullptr,
               *pf4dyn = nullptr, *pf6fix = nullptr, *pf6dyn = nullptr;
     std::map<int, Map *> pols;

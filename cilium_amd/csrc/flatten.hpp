@@ -136,6 +136,11 @@ struct HostImage {
     std::vector<uint4> rnat6;                // 2 per index
     std::vector<uint4> ct6_lb;
     bool lb6_ct = false;                     // ct6_lb wanted
+    // proxy maps for reverse_proxy (layout.h RevTables); rp6: 2 per slot
+    std::vector<uint4> rp4, rp6, rp6_val;
+    std::vector<uint32_t> rp4_val;
+    uint32_t rp4_mask = 0, rp6_mask = 0, n_rp4 = 0, n_rp6 = 0;
+    bool rp_too_big = false;                 // a table would pass RP_MAX_TABLE_BYTES
     uint64_t device_bytes() const;
 };
 
@@ -157,8 +162,16 @@ enum : unsigned {
     GROUP_CT = 8,         // every CT map
     GROUP_IPCACHE6 = 16,  // ipcache, IPv6 LPM
     GROUP_LB = 32,        // cilium_lb{4,6}_services, cilium_lb{4,6}_reverse_nat
-    GROUP_ALL = 63,
+    GROUP_PROXY = 64,     // cilium_proxy4, cilium_proxy6 (reverse_proxy's table)
+    GROUP_ALL = 127,
 };
+// the proxy maps (either may be null) into img's rp4 / rp6 tables
+void build_revproxy(const Map *p4, const Map *p6, HostImage *img);
+// host reference of the device lookup (unit tests): the slot of the key
+// {saddr, ports (dport | sport << 16), nexthdr} in a built table, or -1
+int64_t rp4_find_slot(const HostImage &img, uint32_t saddr, uint32_t ports, uint32_t nexthdr);
+int64_t rp6_find_slot(const HostImage &img, const uint32_t saddr[4], uint32_t ports,
+                      uint32_t nexthdr);
 // maps: every map of the context; groups: which parts of img to build
 // (ct_local, which only depends on which CT maps exist, always is).
 void build_image(const std::vector<Map *> &maps, const BuildOpts &opt,

@@ -208,6 +208,61 @@ __device__ __forceinline__ uint32_t l4_lookup(const DevTables &T, uint32_t a,
     return l4_leaf(T, e);
 }
 
+// ---- IPv6 LPM (layout.h Lpm6): the label of the longest prefix holding the
+// host-order address a (a matched label 0 shadows shorter prefixes, as the
+// reference's trie does), def_label when none
+// The first group's Bloom word is a separate step (lpm6_bloom0) so that the
+// first loads of independent lookups of one header go out together.
+// loff: the dword offset of the table's length list in LDS (LdsPlan6)
+__device__ __forceinline__ uint64_t lpm6_bloom0(const Lpm6 &P, uint32_t loff, uint4 a)
+{
+    if (!P.nlen)
+        return 0;
+    const uint32_t w[4] = {a.x, a.y, a.z, a.w};
+    return P.bloom[l6_group_hash(w, (lds_word(loff) >> 8) & 255) & P.bloom_mask];
+}
+__device__ __forceinline__ uint32_t lpm6_lookup(const Lpm6 &P, uint32_t loff, uint4 a,
+                                                uint64_t bw0)
+{
+    const uint32_t w[4] = {a.x, a.y, a.z, a.w};
+    uint64_t bw = bw0;
+    for (uint32_t j = 0; j < P.nlen; j++) {
+        const uint32_t e = lds_word(loff + j);   // uniform
+        const uint32_t len = e & 255;
+        if ((e & L6_GROUP_FIRST) && j)
+            bw = P.bloom[l6_group_hash(w, (e >> 8) & 255) & P.bloom_mask];
+        const uint32_t m0 = a.x & l6_word_mask(len, 0), m1 = a.y & l6_word_mask(len, 1),
+                       m2 = a.z & l6_word_mask(len, 2), m3 = a.w & l6_word_mask(len, 3);
+        const uint32_t h = l6_hash(m0, m1, m2, m3, len);
+        const uint64_t b = l6_bloom_bits(h);
+        if ((bw & b) != b)
+            continue;
+        if (len <= 64) {   // (uniform) one 16-byte load per probe: {w0, w1, label, len}
+            for (uint32_t s = h & P.mask64;; s = (s + 1) & P.mask64) {
+                const uint4 k = ld16(P.slots64 + s);
+                if (k.w == len && k.x == m0 && k.y == m1)
+                    return k.z;
+                if (!k.w)
+                    break;
+            }
+            continue;
+        }
+        for (uint32_t s = h & P.mask;; s = (s + 1) & P.mask) {
+            const uint4 k = ld16(&P.slots[s].w[0]);
+            const uint4 v = ld16(&P.slots[s].label);   // {label, len, 0, 0}
+            if (v.y == len && k.x == m0 && k.y == m1 && k.z == m2 && k.w == m3)
+                return v.x;
+            if (!v.y)
+                break;
+        }
+    }
+    return P.def_label;
+}
+__device__ __forceinline__ uint32_t lpm6_lookup(const Lpm6 &P, uint32_t loff, uint4 a)
+{
+    return lpm6_lookup(P, loff, a, lpm6_bloom0(P, loff, a));
+}
+
 // ---- endpoint lookup: 16-byte slots, linear probing (layout.h).
 // Returns the slot (info VALID) or a zero slot for a miss.
 __device__ __forceinline__ uint4 lxc_slot(const DevTables &T, const Lds &S,

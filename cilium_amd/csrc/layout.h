@@ -19,6 +19,8 @@
 //   pol       every endpoint's policy table: 16-B slots
 //             {key u64, proxy u16, pad, counter index u32}
 //   lbl_ovf   identities >= 2^30 (rare) referenced from LPM leaves
+//   rp4 / rp6 the proxy maps as reverse_proxy probes them (RevTables below;
+//             read by revproxy.hip only, not part of DevTables)
 //   pf_bloom  blocked Bloom filter over pf4_fix   } copied into LDS by
 //   pol_bloom blocked Bloom filter over all pol   } every workgroup
 // Counters (read-write): u64 packets/bytes per policy entry + metrics.
@@ -445,6 +447,39 @@ __host__ __device__ inline uint32_t lb6_hash(uint32_t a0, uint32_t a1, uint32_t 
 {
     return l6_hash(a0, a1, a2, a3, ps ^ 0x6b43a9b5u);
 }
+
+// ---- proxy maps (cilium_proxy4 / cilium_proxy6) as reverse_proxy /
+// reverse_proxy6 look them up (bpf_netdev.c:67-124, 293-354): the key is
+// {saddr = the packet's daddr, the packet's first L4 word as loaded (dport =
+// its source port, sport = its destination port), nexthdr}.  Open addressing,
+// a power-of-two number of slots, load <= 1/2, linear probing walked to the
+// first free slot (RP_USED clear).
+//   v4 slot (16 B): {saddr, dport | sport << 16, nexthdr | RP_USED,
+//                   orig_daddr}; rp4_val[slot] = orig_dport (be16 raw)
+//   v6 slot (32 B): {saddr words raw}, {dport | sport << 16, nexthdr |
+//                   RP_USED, orig_dport, 0}; rp6_val[slot] = orig_daddr (raw)
+// The value arrays are read on a hit only.  The tables are static per epoch
+// (flatten.cpp build_revproxy); a family without entries has none (null).
+// Not part of DevTables: only the reverse-proxy pass (revproxy.hip) reads it.
+constexpr uint32_t RP_USED = 1u << 8;
+__host__ __device__ inline uint32_t rp4_hash(uint32_t saddr, uint32_t ports, uint32_t nexthdr)
+{
+    return fmix32(fmix32(saddr ^ 0x7ed55d16u) ^ ports ^ nexthdr * 0x01000193u);
+}
+__host__ __device__ inline uint32_t rp6_hash(uint32_t a0, uint32_t a1, uint32_t a2, uint32_t a3,
+                                             uint32_t ports, uint32_t nexthdr)
+{
+    return l6_hash(a0, a1, a2, a3, ports ^ nexthdr * 0x01000193u ^ 0x3c6ef372u);
+}
+struct RevTables {
+    const uint4 *rp4;              // null: cilium_proxy4 empty or not open
+    const uint32_t *rp4_val;
+    const uint4 *rp6;              // 2 uint4 per slot; null: cilium_proxy6 empty
+    const uint4 *rp6_val;
+    uint32_t rp4_mask, rp6_mask;   // slots - 1
+};
+// bytes a raw 16-byte table load may address (kern_common.hpp ldt16)
+constexpr uint64_t RP_MAX_TABLE_BYTES = 1ull << 31;
 
 struct DevTables {
     const uint4 *l4d;              // compact IPv4 LPM directory, or null

@@ -954,8 +954,174 @@ static void pol_direct_kats()
                 printf("pd pol_slot_direct %x %x %x %x\n", pre, d, m, pol_slot_direct(pre, d, m));
 }
 
+// ---- the proxy maps' device tables (flatten.cpp build_revproxy) against a
+// brute-force lookup of the maps themselves
+struct RpKey {
+    uint32_t a[4];       // saddr raw (IPv4: a[0])
+    uint32_t ports;      // dport | sport << 16
+    uint8_t nh;
+};
+static void rp_put(Map &m, bool v6, const RpKey &k, uint32_t tag)
+{
+    uint8_t key[22] = {0}, val[28] = {0};
+    const size_t al = v6 ? 16 : 4;
+    memcpy(key, k.a, al);
+    memcpy(key + al, &k.ports, 4);
+    key[al + 4] = k.nh;
+    uint32_t od[4] = {tag * 2654435761u, tag ^ 0x5555u, tag + 7, ~tag};
+    const uint16_t op = (uint16_t)(tag * 40503u);
+    const uint32_t ident = tag, life = 1;
+    memcpy(val, od, al);
+    memcpy(val + al, &op, 2);
+    memcpy(val + al + 4, &ident, 4);
+    memcpy(val + al + 8, &life, 4);
+    if (m.update(key, val, 0))
+        abort();
+}
+// the table's answer for k against the map's: 0 when they agree
+static int rp_check(const Map &m, const HostImage &img, bool v6, const RpKey &k)
+{
+    uint8_t key[22] = {0}, val[28] = {0};
+    const size_t al = v6 ? 16 : 4;
+    memcpy(key, k.a, al);
+    memcpy(key + al, &k.ports, 4);
+    key[al + 4] = k.nh;
+    const bool have = m.lookup(key, val) == 0;
+    const int64_t s = v6 ? rp6_find_slot(img, k.a, k.ports, k.nh)
+                         : rp4_find_slot(img, k.a[0], k.ports, k.nh);
+    if (!have)
+        return s >= 0;
+    if (s < 0)
+        return 1;
+    uint16_t op;
+    memcpy(&op, val + al, 2);
+    if (v6) {
+        const uint4 od = img.rp6_val[s];
+        return memcmp(&od, val, 16) != 0 || img.rp6[2 * s + 1].z != op;
+    }
+    return memcmp(&img.rp4[s].w, val, 4) != 0 || img.rp4_val[s] != op;
+}
+static RpKey rp_rand(std::mt19937 &gen, bool v6)
+{
+    RpKey k{{(uint32_t)gen(), v6 ? (uint32_t)gen() : 0u, v6 ? (uint32_t)gen() : 0u,
+             v6 ? (uint32_t)gen() : 0u},
+            (uint32_t)gen(), (uint8_t)((gen() & 1) ? 6 : 17)};
+    return k;
+}
+static uint32_t rp_home(const RpKey &k, bool v6, uint32_t mask)
+{
+    return (v6 ? rp6_hash(k.a[0], k.a[1], k.a[2], k.a[3], k.ports, k.nh)
+               : rp4_hash(k.a[0], k.ports, k.nh)) & mask;
+}
+static int rp_case(const char *name, bool v6, const std::vector<RpKey> &keys,
+                   const std::vector<RpKey> &absent, uint32_t want_slots, bool want_wrap)
+{
+    Map m;
+    m.type = MT_HASH, m.ksz = v6 ? 22 : 10, m.vsz = v6 ? 28 : 16, m.max_entries = 1u << 20;
+    m.role = v6 ? ROLE_PROXY6 : ROLE_PROXY4;
+    for (size_t i = 0; i < keys.size(); i++)
+        rp_put(m, v6, keys[i], (uint32_t)i + 1);
+    HostImage img;
+    build_revproxy(v6 ? nullptr : &m, v6 ? &m : nullptr, &img);
+    const uint32_t slots = v6 ? (uint32_t)img.rp6_val.size() : (uint32_t)img.rp4.size();
+    const uint32_t mask = v6 ? img.rp6_mask : img.rp4_mask, n = v6 ? img.n_rp6 : img.n_rp4;
+    int bad = slots != want_slots || n != keys.size() || (slots && mask != slots - 1) ||
+              (slots & (slots - 1)) || 2 * n > slots;
+    bad |= (v6 ? img.rp4.size() : img.rp6.size()) != 0;   // the other family: no table
+    uint32_t used = 0, wraps = 0;
+    for (uint32_t s = 0; s < slots; s++)
+        used += ((v6 ? img.rp6[2 * s + 1].y : img.rp4[s].z) & RP_USED) != 0;
+    bad |= used != n;
+    for (const RpKey &k : keys) {
+        bad |= rp_check(m, img, v6, k);
+        const int64_t s = v6 ? rp6_find_slot(img, k.a, k.ports, k.nh)
+                             : rp4_find_slot(img, k.a[0], k.ports, k.nh);
+        wraps += s >= 0 && (uint32_t)s < rp_home(k, v6, mask);
+    }
+    for (const RpKey &k : absent)
+        bad |= rp_check(m, img, v6, k);
+    bad |= want_wrap && !wraps;
+    printf("revproxy %-10s v%d %zu entries, %u slots, %zu absent keys, %u wrapped -> %s\n", name,
+           v6 ? 6 : 4, keys.size(), slots, absent.size(), wraps, bad ? "FAIL" : "ok");
+    return bad;
+}
+static int revproxy_tests()
+{
+    std::mt19937 gen(777);   // (its own stream: the same cases alone and in the whole run)
+    int fail = 0;
+    for (int f = 0; f < 2; f++) {
+        const bool v6 = f != 0;
+        auto absent_of = [&](const std::vector<RpKey> &keys) {
+            // random keys, and every key with exactly one field changed
+            std::vector<RpKey> q;
+            for (int i = 0; i < 64; i++)
+                q.push_back(rp_rand(gen, v6));
+            for (const RpKey &k : keys) {
+                if (q.size() > 4000)
+                    break;
+                RpKey a = k, d = k, s = k, p = k;
+                a.a[v6 ? 3 : 0] ^= 0x01000000u;
+                d.ports ^= 0x0100u;
+                s.ports ^= 0x01000000u;
+                p.nh = k.nh == 6 ? 17 : 6;
+                q.insert(q.end(), {a, d, s, p});
+            }
+            return q;
+        };
+        // 0, 1, 2 entries; a power of two and one above it (2n slots: the
+        // slot count doubles between them)
+        const uint32_t sizes[][2] = {{0, 0}, {1, 2}, {2, 4}, {4, 8}, {5, 16}, {64, 128},
+                                     {65, 256}, {1000, 2048}};
+        for (auto &sz : sizes) {
+            std::vector<RpKey> keys;
+            for (uint32_t i = 0; i < sz[0]; i++)
+                keys.push_back(rp_rand(gen, v6));
+            char name[32];
+            snprintf(name, sizeof name, "n%u", sz[0]);
+            fail |= rp_case(name, v6, keys, absent_of(keys), sz[1], false);
+        }
+        {   // entries that differ in exactly one field each: all present, each its own value
+            const RpKey k = rp_rand(gen, v6);
+            RpKey a = k, d = k, s = k, p = k;
+            a.a[v6 ? 2 : 0] ^= 0x00010000u;
+            d.ports ^= 0x0001u;
+            s.ports ^= 0x00010000u;
+            p.nh = k.nh == 6 ? 17 : 6;
+            const std::vector<RpKey> keys = {k, a, d, s, p};
+            fail |= rp_case("one-field", v6, keys, absent_of(keys), 16, false);
+        }
+        {   // a probe chain that wraps the end of the table: three keys whose
+            // home is the last of 8 slots, and a fourth elsewhere
+            std::vector<RpKey> keys;
+            while (keys.size() < 3) {
+                const RpKey k = rp_rand(gen, v6);
+                if (rp_home(k, v6, 7) == 7)
+                    keys.push_back(k);
+            }
+            for (;;) {
+                const RpKey k = rp_rand(gen, v6);
+                if (rp_home(k, v6, 7) == 3) {
+                    keys.push_back(k);
+                    break;
+                }
+            }
+            // absent keys that start on the chain and walk it to its free end
+            std::vector<RpKey> q = absent_of(keys);
+            while (q.size() < 100) {
+                const RpKey k = rp_rand(gen, v6);
+                if (rp_home(k, v6, 7) == 7 || rp_home(k, v6, 7) == 0)
+                    q.push_back(k);
+            }
+            fail |= rp_case("wrap", v6, keys, q, 8, true);
+        }
+    }
+    return fail;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc > 1 && !strcmp(argv[1], "revproxy"))   // the proxy maps' tables alone
+        return revproxy_tests();
     if (argc > 1 && !strcmp(argv[1], "poldirect")) {   // the direct policy placement alone
         pol_direct_kats();
         return pol_direct_tests();
@@ -1029,5 +1195,6 @@ int main(int argc, char **argv)
     fail |= pol_direct_tests();
     fail |= ReplayCase<false>().run();
     fail |= ReplayCase<true>().run();
+    fail |= revproxy_tests();
     return fail;
 }

@@ -73,6 +73,14 @@ class Verdicts:
     pkt_raw: "torch.Tensor | None" = None
 
 
+@dataclasses.dataclass
+class Translated:
+    """What classify_from_host leaves beside the verdicts (cfc_revproxy_cols)."""
+    batch: "HeaderBatchV4 | HeaderBatchV6"   # the translated header batch
+    identity: "torch.Tensor"    # int32, written on hit rows only
+    hits: "torch.Tensor | None" = None   # int64 (1,): translated rows
+
+
 def pack_v4(h, device="cuda"):
     """synth.Headers (numpy) -> HeaderBatchV4 on `device`."""
     import numpy as np
@@ -398,6 +406,57 @@ class Datapath:
             return self.classify_v6(batch, mode, ep_lxc, **kw)
         return self.classify_v4(batch, mode, ep_lxc, **kw)
 
+    def classify_from_host(self, batch, out: Verdicts | None = None, alias=False,
+                           want_hits=True, tr: "Translated | None" = None,
+                           want_action=True, want_ct=False, want_notify=False,
+                           stream=None):
+        """cfc_classify_from_host_v4/v6: reverse_proxy over a from-host batch
+        (the L7 proxy's packets towards an endpoint get the source of the
+        connection the proxy stands in for, from cilium_proxy4/6 as of the
+        last commit()), then INGRESS classification of the translated batch
+        -> (Verdicts, Translated).  Translated.batch is the header batch to
+        hand to ct_apply, monitor_events, drop_notify and proxy_entries (mode
+        INGRESS).  alias=True translates in place: saddr, ports and mark are
+        the batch's own tensors (a mark column is then required) and only
+        hit rows are written; otherwise new tensors get every row.  Pass `tr`
+        to choose the columns yourself."""
+        import torch
+        v6 = isinstance(batch, HeaderBatchV6)
+        n = len(batch)
+        dev = batch.ports.device
+        new = lambda *shape, dt=torch.int32: torch.empty(*shape, dtype=dt, device=dev)  # noqa: E731
+        if out is None:
+            out = Verdicts(new(n), new(n), new(n, dt=torch.uint8) if want_action else None,
+                           new(n, dt=torch.uint8) if want_ct else None,
+                           new(n) if want_notify else None)
+        if tr is None:
+            if alias:
+                assert batch.mark is not None, "in-place translation needs a mark column"
+                cols = (batch.saddr, batch.ports, batch.mark)
+            else:
+                cols = (new(n, 4) if v6 else new(n), new(n), new(n))
+            tb = dataclasses.replace(batch, saddr=cols[0], ports=cols[1], mark=cols[2])
+            tr = Translated(tb, torch.zeros(n, dtype=torch.int32, device=dev),
+                            torch.zeros(1, dtype=torch.int64, device=dev) if want_hits else None)
+        tb = tr.batch
+        for t in (batch.saddr, batch.daddr, batch.ports, batch.meta, tb.saddr, tb.ports,
+                  tb.mark, tr.identity):
+            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.int32
+        assert tb.saddr.numel() == batch.saddr.numel() == (4 * n if v6 else n)
+        assert tb.ports.numel() == tb.mark.numel() == tr.identity.numel() == n
+        assert tb.daddr is batch.daddr and tb.meta is batch.meta
+        if v6:
+            assert batch.saddr.data_ptr() % 16 == 0 and batch.daddr.data_ptr() % 16 == 0
+            assert tb.saddr.data_ptr() % 16 == 0
+        cols = L.RevproxyCols(_ptr(tb.saddr), _ptr(tb.ports), _ptr(tb.mark),
+                              _ptr(tr.identity), _ptr(tr.hits))
+        hdr = hdr_struct(batch)
+        o = out_struct(out)
+        fn = self.L.cfc_classify_from_host_v6 if v6 else self.L.cfc_classify_from_host_v4
+        L.check(fn(self.h, ctypes.byref(hdr), ctypes.byref(cols), ctypes.byref(o),
+                   self._stream(stream)), "classify from host")
+        return out, tr
+
     def ct_apply(self, batch, out: Verdicts, mode=L.MODE_INGRESS, ep_lxc=0,
                  stream=None):
         """cfc_ct_apply_v4/v6: fold a classified batch (out.ct set) into the
@@ -605,5 +664,5 @@ def errno_name(e: OSError):
     return errno.errorcode.get(e.errno, str(e.errno))
 
 
-__all__ = ["Datapath", "HeaderBatchV4", "HeaderBatchV6", "Verdicts", "pack_v4",
+__all__ = ["Datapath", "HeaderBatchV4", "HeaderBatchV6", "Verdicts", "Translated", "pack_v4",
            "pack_v6", "pack", "host_only", "errno_name"]

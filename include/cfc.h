@@ -75,8 +75,10 @@ int cfc_abi_version(void);
  *   cilium_lb4_reverse_nat  HASH key 2 (rev_nat_index) value 6 (struct
  *                           lb4_reverse_nat {address, port})
  *   cilium_proxy4           HASH key 10 (struct proxy4_tbl_key) value 16
- *                           (struct proxy4_tbl_value); a host map with no
- *                           device table, written by cfc_proxy_apply_v4
+ *                           (struct proxy4_tbl_value); written by
+ *                           cfc_proxy_apply_v4, looked up by
+ *                           cfc_classify_from_host_v4 (its device table is
+ *                           flattened by an explicit cfc_commit)
  *   cilium_proxy6           HASH key 22 (struct proxy6_tbl_key) value 28
  *                           (struct proxy6_tbl_value); cfc_proxy_apply_v6
  * Any other name is a plain map with no datapath role.  Opening an existing
@@ -153,8 +155,10 @@ int cfc_get_node_config(cfc_ctx *ctx, cfc_node_config *cfg);
 int cfc_set_clock(cfc_ctx *ctx, uint32_t now_sec);
 
 /* Publish the maps' changes to the device (the first classify after a
- * change commits by itself).  The device tables form five groups —
- * ipcache IPv4, ipcache IPv6, prefilter, endpoints + policymaps, conntrack —
+ * change commits by itself).  The device tables form groups —
+ * ipcache IPv4, ipcache IPv6, prefilter, endpoints + policymaps, conntrack,
+ * load balancing, and the proxy maps (which only this call re-flattens, not
+ * a classify's auto-commit: "From-host batches" below) —
  * and a commit re-flattens only the groups whose maps changed.  A value
  * overwritten in place (an existing IPv6 ipcache prefix's identity, an
  * existing policy entry's proxy port) is patched into the live tables
@@ -683,6 +687,87 @@ int cfc_proxy_apply_v4(cfc_ctx *ctx, const cfc_hdr_v4 *in, const cfc_out *out,
 int cfc_proxy_apply_v6(cfc_ctx *ctx, const cfc_hdr_v6 *in, const cfc_out *out,
                        int mode, uint16_t ep_lxc, cfc_proxy_stats *st,
                        void *stream);
+
+/* ---------------------------------------------------- from-host batches */
+/* The other half of a redirect's round trip.  The proxy's own packets
+ * towards an endpoint come back through bpf_netdev.c from-host, where
+ * handle_ipv4 / handle_ipv6 (:400-416, :218-234) run reverse_proxy /
+ * reverse_proxy6 (:293-354, :67-124) before local delivery:
+ *   lookup   TCP and UDP only (IPv6: by ip6->nexthdr, the first next header,
+ *            so a header with CFC_HF_EXTHDR is never looked up; CFC_HF_FRAG
+ *            headers are, like any other), with the key {saddr = the
+ *            packet's daddr, dport = its source port, sport = its
+ *            destination port, nexthdr, pad 0} in cilium_proxy4 /
+ *            cilium_proxy6 — the entry cfc_proxy_apply_* wrote when the
+ *            connection was redirected.  `lifetime` is not checked (the
+ *            reference does not; only the GC removes entries).
+ *   on a hit the source address becomes orig_daddr, the source port
+ *            orig_dport (bits 0-15 of the L4 word; bits 16-31 stay), and
+ *            TC_INDEX_F_SKIP_PROXY is set: the endpoint's ingress policy
+ *            must not redirect the packet again.
+ * CT lookup, policy and records of the endpoint's ipv{4,6}_policy then all
+ * see the rewritten packet.  The source identity was settled before the
+ * rewrite — handle_identity_from_host's from the mark, overridden by the
+ * ipcache label of the ORIGINAL source when it is reserved (IPv4 ignores
+ * the labels 0, CLUSTER_ID and HOST_ID, :375-398; IPv6 only 0 and
+ * CLUSTER_ID, :203-213) — so a translated header carries it in a column of
+ * its own instead of having it derived from its (new) source.
+ *
+ * The lookups read a device table flattened from the two maps by
+ * cfc_commit(), and ONLY by an explicit cfc_commit() (a classify's
+ * auto-commit leaves it alone once the context has tables): an entry written by cfc_proxy_apply_* or
+ * through the map API translates after the next cfc_commit(), a deleted one
+ * until then.  The table is rebuilt only when a proxy map changed.
+ *
+ * CFC_MARK_TRANSLATED: bit 12 of the mark column, outside
+ * MARK_MAGIC_HOST_MASK (0xF00) and outside the identity bits of a proxy mark
+ * (0-7 and 16-31).  A translated header's mark is 0xA00 |
+ * CFC_MARK_TRANSLATED, whatever it was: 0xA00 (MARK_MAGIC_PROXY_INGRESS)
+ * carries skip-proxy through every later call (a NAT46 hop included), bit
+ * 12 tells cfc_classify_from_host_*'s own classify launch to take the
+ * identity column as it stands.  The marks a caller passes in must have the
+ * bit clear.  cfc_classify_v4/v6 ignore it, as they always have.
+ *
+ * cfc_revproxy_cols: the translated columns (device memory, n elements).
+ * saddr, ports and mark may each be the batch's own column (in->saddr,
+ * in->ports, in->mark): a column that aliases its input is written on hit
+ * rows only, any other on every row (a miss copies its input; with in->mark
+ * NULL the mark of a miss is 0).
+ *   saddr    n u32 (IPv6: n 16-byte rows, 16-byte aligned)
+ *   ports    the first L4 word
+ *   mark     required even when in->mark is NULL
+ *   identity required; written on hit rows only: the final source identity
+ *   hits     (may be NULL) device u64: receives the number of hit rows
+ */
+#define CFC_MARK_TRANSLATED 0x1000u
+typedef struct {
+    void *saddr;
+    uint32_t *ports;
+    uint32_t *mark;
+    uint32_t *identity;
+    uint64_t *hits;
+} cfc_revproxy_cols;
+/* One call: the lookup pass, then CFC_MODE_INGRESS classification (the only
+ * mode: from-host traffic never passed bpf_xdp) of the translated batch
+ *   {tr->saddr, in->daddr, tr->ports, in->meta, tr->mark, in->tcp_flags,
+ *    in->n, in->hash}
+ * exactly as cfc_classify_v4/v6 would run it, except that rows with
+ * CFC_MARK_TRANSLATED take tr->identity.  Pass that translated header (and
+ * `out`, mode CFC_MODE_INGRESS, ep_lxc 0) to cfc_ct_apply_*,
+ * cfc_monitor_events_*, cfc_drop_notify_* and cfc_proxy_entries_*: none of
+ * them derives an identity again.  The records' flow hash is taken over the
+ * translated header unless in->hash is given.  With empty (or unopened)
+ * proxy maps no lookup kernel runs — columns that do not alias are copied,
+ * *hits is zeroed — and the outputs equal cfc_classify_*'s.
+ * Asynchronous on `stream`.  -EINVAL: a NULL tr, tr->saddr, ports, mark or
+ * identity (or, as cfc_classify_*, header or output column), a misaligned
+ * IPv6 row; -ENODEV on a host-only context. */
+int cfc_classify_from_host_v4(cfc_ctx *ctx, const cfc_hdr_v4 *in,
+                              const cfc_revproxy_cols *tr, const cfc_out *out,
+                              void *stream);
+int cfc_classify_from_host_v6(cfc_ctx *ctx, const cfc_hdr_v6 *in,
+                              const cfc_revproxy_cols *tr, const cfc_out *out,
+                              void *stream);
 
 /* ---------------------------------------------------------------- counters */
 /* The device counter block is a flat u64 array:
