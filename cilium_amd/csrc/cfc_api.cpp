@@ -1932,7 +1932,7 @@ int nat_hop(cfc_ctx *c, const DevTables &T, const EgressArgs &ea, const Hdr &in,
     e2.sums = nullptr;
     e2.svo = nullptr;   // (the hop rows are another batch)
     const int smode = V6 ? CFC_MODE_EGRESS : CFC_MODE_INGRESS;
-    const WsLayout wl = ws_layout(m, T, smode, true);
+    const WsLayout wl = ws_layout(m, T, smode, true, c->num_cus);
     if (r.ws.ensure(wl.total))
         return -ENOMEM;
     DevTables Th = T;   // (a hop launch keeps no plain-hit summaries)
@@ -1996,7 +1996,7 @@ int nat_hop(cfc_ctx *c, const DevTables &T, const EgressArgs &ea, const Hdr &in,
         const bool egr = mode == CFC_MODE_EGRESS;
         cfc_hdr_v4 gin = in;
         if (egr && (T.lb4 || T.rnat4)) {
-            const WsLayout lw = ws_layout(in.n, T, mode, true);
+            const WsLayout lw = ws_layout(in.n, T, mode, true, c->num_cus);
             const uint32_t *a = (const uint32_t *)((const char *)c->ws + lw.lb);
             const uint64_t st = (in.n + 3) & ~3ull;   // (ctr_stride: one u32 per header)
             gin.saddr = a + 2 * st;   // (LbArgs: tda, tpt, psa, pda, ppt, fl)
@@ -2102,7 +2102,8 @@ int classify_one(cfc_ctx *c, const Hdr *in, const cfc_out *out, int mode,
     }
     const WsLayout wl = ws_layout(in->n, E.T, mode,
                                   E.T.ct4 || E.T.ct6 || out->ct || E.T.lb4 || E.T.rnat4 ||
-                                      E.T.lb6 || E.T.rnat6);
+                                      E.T.lb6 || E.T.rnat6,
+                                  c->num_cus);
     const size_t need = wl.total;
     c->last_cls.valid = false;
     if (need > c->ws_bytes) {

@@ -691,6 +691,42 @@ __device__ __forceinline__ void acc_publish(const unsigned long long *s_met,
     }
 }
 
+// One step of a wave's compact key stream (classify.hpp key_regions): the
+// lanes whose key is live store it behind the `cur` words the wave has
+// appended to its region so far, in lane order.  cur is wave-uniform (it only
+// ever moves by a ballot's popcount), so it lives in an SGPR.
+#ifndef CFC_KEY_NT
+#define CFC_KEY_NT 1   // non-temporal appends (0: plain stores; A/B builds)
+#endif
+// Which key arrays the kernel writes compact (KEYS_*).  The policy stream
+// alone: at C2 0.135 of its words are live and k_hist's policy job is bound
+// by the bytes it streams.  The identity job is bound by its LDS atomics, so
+// compacting that stream too (KEYS_CTR | KEYS_ID, an A/B build) gains 4 us in
+// k_hist and costs the classify kernel 30 us; 0 keeps a word
+// per header in every array, as the IPv6 kernel.
+#ifndef CFC_KEYS_COMPACT
+#define CFC_KEYS_COMPACT KEYS_CTR
+#endif
+__device__ __forceinline__ uint32_t key_wave()   // the wave's index in its workgroup
+{
+    return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+}
+__device__ __forceinline__ void key_append(uint32_t key, bool valid, uint32_t *region,
+                                           uint32_t &cur)
+{
+    const bool live = valid && key != KEY_NONE;
+    const uint64_t m = __ballot(live);
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi(
+        (uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    if (live) {
+        if (CFC_KEY_NT)
+            sto_nt(key, region, (cur + rank) << 2);
+        else
+            sto(key, region, (cur + rank) << 2);
+    }
+    cur += (uint32_t)__popcll(m);
+}
+
 // OPT: the call passes some optional array (mark, tcp_flags, action, ct);
 // without, their pointers and branches are compiled out (fewer live SGPRs)
 // LB: the launch has a load balancer — an egress batch reads the service
@@ -790,12 +826,21 @@ __global__ __launch_bounds__(BLOCK, WAVES_PER_SIMD) void k_classify_v4(
         C.ct += start;
     if (C.ct2)
         C.ct2 += start;
-    if (C.ctr)
-        C.ctr += start;
-    if (C.ctr2)
-        C.ctr2 += start;
-    if (C.id)
-        C.id += start;
+    // a compact key array (classify.hpp key_regions): advanced to this wave's
+    // region, inside the workgroup's slice; kn_*: the wave's append cursors
+    // (the policy keys only when packed, CountArgs.compact)
+    constexpr bool KC = (CFC_KEYS_COMPACT & KEYS_ID) != 0;
+    const bool kc_ctr = (CFC_KEYS_COMPACT & KEYS_CTR) && C.ctr_packed;
+    uint32_t kn_ctr = 0, kn_ctr2 = 0, kn_id = 0;
+    {
+        const uint32_t at = key_wave() * key_regions_grid(gridDim.x, per_block).cap;
+        if (C.ctr)
+            C.ctr += start + (kc_ctr ? at : 0u);
+        if (C.ctr2)
+            C.ctr2 += start + (kc_ctr ? at : 0u);
+        if (C.id)
+            C.id += start + (KC ? at : 0u);
+    }
     if (TR)
         tr_id += start;
     // the trip count is uniform across the workgroup (the metrics flush
@@ -859,15 +904,27 @@ __global__ __launch_bounds__(BLOCK, WAVES_PER_SIMD) void k_classify_v4(
                 }
                 if (MODE != CFC_MODE_XDP) {
 #if CFC_EXP != 3
-                    sto_nt(ctr_key(C, h[u].ctr0, len), C.ctr, o4);
-#endif
-                    if (EGR)
-                        sto_nt(ctr_key(C, h[u].ctr1, len), C.ctr2, o4);
-#if CFC_EXP != 3
-                    sto_nt(h[u].idw, C.id, o4);
+                    if (!kc_ctr) {   // (uniform)
+                        sto_nt(ctr_key(C, h[u].ctr0, len), C.ctr, o4);
+                        if (EGR)
+                            sto_nt(ctr_key(C, h[u].ctr1, len), C.ctr2, o4);
+                    }
+                    if (!KC)
+                        sto_nt(h[u].idw, C.id, o4);
 #endif
                 }
             }
+#if CFC_EXP != 3
+            if (MODE != CFC_MODE_XDP) {   // the live key words, appended
+                if (kc_ctr) {
+                    key_append(ctr_key(C, h[u].ctr0, len), h[u].valid, C.ctr, kn_ctr);
+                    if (EGR)
+                        key_append(ctr_key(C, h[u].ctr1, len), h[u].valid, C.ctr2, kn_ctr2);
+                }
+                if (KC)
+                    key_append(h[u].idw, h[u].valid, C.id, kn_id);
+            }
+#endif
             if (WL && E.wbits) {   // (uniform) the wave's 64 headers' work bits
                 bool pr;
                 const bool w = wl_want<EGR>(h[u].ct_byte, h[u].ver, h[u].mt, h[u].ct_k1,
@@ -903,6 +960,23 @@ __global__ __launch_bounds__(BLOCK, WAVES_PER_SIMD) void k_classify_v4(
         }
     }
     acc.flush(s_met);
+    if (CFC_KEYS_COMPACT && MODE != CFC_MODE_XDP && (threadIdx.x & 63) == 0) {
+        // the regions' counts (KeyRegions::counts): from the wave's own
+        // region, to the end of the last workgroup's slice and then
+        // KEY_WAVES * blockIdx.x + wave words on
+        const uint32_t wave = key_wave();
+        const uint64_t to_counts =
+            (uint64_t)(gridDim.x - blockIdx.x) * per_block -
+            (uint64_t)wave * key_regions_grid(gridDim.x, per_block).cap +
+            (uint64_t)blockIdx.x * KEY_WAVES + wave;
+        if (kc_ctr) {
+            C.ctr[to_counts] = kn_ctr;
+            if (EGR)
+                C.ctr2[to_counts] = kn_ctr2;
+        }
+        if (KC)
+            C.id[to_counts] = kn_id;
+    }
     __syncthreads();
     acc_publish<MODE>(s_met, C, E.seclabel);
 }
@@ -934,6 +1008,14 @@ struct HistJob {
     uint32_t lo, cnt;     // key range [lo, lo + cnt)
     uint32_t kind;        // 0 policy entry, 1 identity (dense << 1 | drop)
     uint32_t packed;      // keys carry len in bits 16-31 (else meta does)
+    // The job's position space [0, n) in slices of per_block (a multiple of
+    // 4).  A dense job: one key word per header.  A compact job (classify.hpp
+    // key_regions; always packed): n is the regions' extent, cap a region's
+    // words, and position i holds a key iff i % cap < counts[i / cap] — any
+    // other word is stale workspace and is never looked at.
+    uint32_t compact, cap;
+    const uint32_t *counts;
+    uint64_t n, per_block;
 };
 constexpr int HIST_JOBS_MAX = 12;
 struct HistJobs {
@@ -1026,8 +1108,59 @@ __device__ __forceinline__ void hist_escape(const HistLds &L, const HistJob &jb,
         atomicAdd(d + 1, (unsigned long long)HistSlot::esc_bytes(carry));
 }
 
+// A compact job's slice [start, stop) of the regions' position space
+// (classify.hpp key_regions).  The workgroup's waves take the regions that
+// overlap the slice in turn; a wave reads its region's count (wave-uniform)
+// and then only the words below it that lie in the slice, 256 per step with
+// the next two steps' loads in flight.  Nothing at or past the count is
+// looked at: the tail of a step's last 16 bytes is masked by position, and a
+// lane past the live words re-reads the last live 16 bytes (so every lane
+// issues every load, and the loads retire in a known order).
+__device__ __forceinline__ void hist_compact(const HistLds &L, const HistJob &jb,
+                                             uint64_t start, uint64_t stop, uint64_t *g_ctr,
+                                             uint64_t *g_id, uint32_t id_dir)
+{
+    if (start >= stop)
+        return;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t lane4 = 4 * (threadIdx.x & 63);
+    const uint32_t r1 = (uint32_t)((stop + jb.cap - 1) / jb.cap);   // regions of the slice: end
+    uint32_t r = (uint32_t)(start / jb.cap) + wave;
+    uint32_t cnt = r < r1 ? jb.counts[r] : 0u;
+    while (r < r1) {
+        const uint32_t rn = r + KEY_WAVES;   // (its count behind this region's steps)
+        const uint32_t cnt_n = rn < r1 ? jb.counts[rn] : 0u;
+        const uint64_t rb = (uint64_t)r * jb.cap;
+        const uint64_t lo = max(rb, start), hi = min(rb + min(cnt, jb.cap), stop);
+        if (lo < hi) {   // (uniform) lo: a multiple of 4, as start and rb are
+            const uint32_t len = (uint32_t)(hi - lo), last = (len - 1) & ~3u;
+            const uint32_t *k = jb.keys + lo;
+            uint4 w0 = ld_nt4(k + min(lane4, last));
+            uint4 w1 = ld_nt4(k + min(lane4 + 256, last));
+            for (uint32_t o = lane4, b = 0; b < len; b += 256, o += 256) {
+                const uint4 w2 = ld_nt4(k + min(o + 512, last));
+                // the four atomics issue back to back; their returns are
+                // looked at once, after the last
+                const HistAdd a0 = hist_add(L.s, jb, o < len ? w0.x : KEY_NONE, 0u);
+                const HistAdd a1 = hist_add(L.s, jb, o + 1 < len ? w0.y : KEY_NONE, 0u);
+                const HistAdd a2 = hist_add(L.s, jb, o + 2 < len ? w0.z : KEY_NONE, 0u);
+                const HistAdd a3 = hist_add(L.s, jb, o + 3 < len ? w0.w : KEY_NONE, 0u);
+                if (hist_spills(a0) | hist_spills(a1) | hist_spills(a2) | hist_spills(a3)) {
+                    hist_escape(L, jb, a0, g_ctr, g_id, id_dir);
+                    hist_escape(L, jb, a1, g_ctr, g_id, id_dir);
+                    hist_escape(L, jb, a2, g_ctr, g_id, id_dir);
+                    hist_escape(L, jb, a3, g_ctr, g_id, id_dir);
+                }
+                w0 = w1;
+                w1 = w2;
+            }
+        }
+        r = rn;
+        cnt = cnt_n;
+    }
+}
+
 __global__ __launch_bounds__(BLOCK) void k_hist(HistJobs J, const uint32_t *meta,
-                                                uint64_t n, uint64_t per_block,
                                                 uint32_t *partial, uint64_t *g_ctr,
                                                 uint64_t *g_id, uint32_t id_dir)
 {
@@ -1042,8 +1175,11 @@ __global__ __launch_bounds__(BLOCK) void k_hist(HistJobs J, const uint32_t *meta
     for (uint32_t j = threadIdx.x; j < jb.cnt; j += BLOCK)
         s[j] = 0;
     __syncthreads();
-    const uint64_t start = (uint64_t)blockIdx.x * per_block;   // multiple of 4
-    const uint64_t end = min(n, start + per_block);
+    const uint64_t start = (uint64_t)blockIdx.x * jb.per_block;   // multiple of 4
+    const uint64_t stop = max(start, min(jb.n, start + jb.per_block));
+    if (jb.compact)   // (uniform)
+        hist_compact(L, jb, start, stop, g_ctr, g_id, id_dir);
+    const uint64_t end = jb.compact ? start : stop;   // a dense job: a word per header
     const uint64_t end4 = start + ((end - start) & ~3ull);
     const bool meta16 = (reinterpret_cast<uintptr_t>(meta) & 15) == 0;
     // the loads of the next two steps are in flight during this step's LDS
@@ -1939,22 +2075,26 @@ uint32_t ctp_buckets(const DevTables &T)
     return nb <= CTP_MAX_BUCKETS ? (uint32_t)nb : 0u;
 }
 
-WsLayout ws_layout(uint64_t n, const DevTables &T, int mode, bool ct)
+WsLayout ws_layout(uint64_t n, const DevTables &T, int mode, bool ct, int num_cus)
 {
     WsLayout w{};
     if (n == 0 || mode == CFC_MODE_XDP)
         return w;
     const bool egr = mode == CFC_MODE_EGRESS;
     const size_t a = 4 * ctr_stride(n);   // one u32 per header, 16-B aligned
+    // ... or an IPv4 launch's regions up to the last workgroup's, and counts
+    w.key_pb = key_per_block(n, (uint64_t)std::max(num_cus, 1) * CFC_WG_PER_CU,
+                             (uint64_t)BLOCK * CFC_UNROLL);
+    const size_t ka = std::max<size_t>(a, 4 * key_regions(n, w.key_pb).words());
     size_t off = 0;
     w.ctr = off;
-    off += a;
+    off += ka;
     if (egr) {
         w.ctr2 = off;
-        off += a;
+        off += ka;
     }
     w.id = off;
-    off += a;
+    off += ka;
     if (ct) {
         w.ct = off;
         off += a;
@@ -2003,7 +2143,7 @@ WsLayout ws_layout(uint64_t n, const DevTables &T, int mode, bool ct)
 }
 
 CountArgs count_args(uint32_t *ws, const WsLayout &w, const DevTables &T,
-                     uint64_t *g_met, int mode, bool ct)
+                     uint64_t *g_met, int mode, bool ct, bool v4)
 {
     CountArgs C{};
     char *b = reinterpret_cast<char *>(ws);
@@ -2018,6 +2158,10 @@ CountArgs count_args(uint32_t *ws, const WsLayout &w, const DevTables &T,
     C.g_met = g_met;
     C.g_id = g_met + METRIC_U64;
     C.ctr_packed = T.n_ctr < PACK_MAX;
+    // (unpacked policy keys stay dense: k_hist reads their len from meta by
+    // header index)
+    if (v4 && w.total)
+        C.compact = CFC_KEYS_COMPACT & (KEYS_ID | (C.ctr_packed ? KEYS_CTR : 0u));
     return C;
 }
 
@@ -2031,13 +2175,10 @@ int launch_classify_v4(const DevTables &T, const cfc_hdr_v4 &in,
     if (classify_lds_bytes(T) > LDS_PER_WG)
         return -22;
     // CFC_WG_PER_CU workgroups per CU (the LDS image allows no more), a
-    // contiguous slice each, rounded to whole loop iterations
-    const uint64_t step = (uint64_t)BLOCK * CFC_UNROLL;
-    const uint64_t nwg = (uint64_t)num_cus * CFC_WG_PER_CU;
-    uint64_t per_block = (in.n + nwg - 1) / nwg;
-    per_block = (per_block + step - 1) / step * step;
-    // slices stay below 2^30 headers (32-bit byte offsets in the kernel)
-    per_block = std::min<uint64_t>(per_block, (1ull << 30) / step * step);
+    // contiguous slice each (key_per_block; ws_layout sizes the key arrays
+    // by the same)
+    const uint64_t per_block = key_per_block(in.n, (uint64_t)std::max(num_cus, 1) * CFC_WG_PER_CU,
+                                             (uint64_t)BLOCK * CFC_UNROLL);
     const uint32_t grid = (uint32_t)((in.n + per_block - 1) / per_block);
     if (tm)
         (void)hipEventRecord(tm->ev[0], s);
@@ -2047,8 +2188,8 @@ int launch_classify_v4(const DevTables &T, const cfc_hdr_v4 &in,
     // reverse NAT) and runs the LB variant
     const bool lb = (T.lb4 || T.rnat4) && mode != CFC_MODE_XDP;
     const bool ct = T.ct4 || out.ct || lb;
-    const WsLayout w = ws_layout(in.n, T, mode, ct);
-    const CountArgs C = count_args(ws, w, T, g_ctr + 2ull * T.n_ctr, mode, ct);
+    const WsLayout w = ws_layout(in.n, T, mode, ct, num_cus);
+    const CountArgs C = count_args(ws, w, T, g_ctr + 2ull * T.n_ctr, mode, ct, true);
     cfc_hdr_v4 hin = in;
     LbIn li{};
     if (lb && mode == CFC_MODE_EGRESS) {
@@ -2085,7 +2226,8 @@ int launch_classify_v4(const DevTables &T, const cfc_hdr_v4 &in,
 #undef CFC_LAUNCH
     if (tm)
         (void)hipEventRecord(tm->ev[1], s);
-    const bool sums = launch_counters(T, in.meta, in.tcp_flags, in.n, mode, ws, g_ctr, s, ct);
+    const bool sums = launch_counters(T, in.meta, in.tcp_flags, in.n, mode, ws, g_ctr, s, ct,
+                                      C, w);
     if (E.sums)
         *E.sums = sums;
     if (tm)
@@ -2096,13 +2238,11 @@ int launch_classify_v4(const DevTables &T, const cfc_hdr_v4 &in,
 
 bool launch_counters(const DevTables &T, const uint32_t *meta, const uint8_t *tf, uint64_t n,
                      int mode, uint32_t *ws, uint64_t *g_ctr, hipStream_t s,
-                     bool ct)
+                     bool ct, const CountArgs &C, const WsLayout &w)
 {
     bool sums = false;
     if (!n || mode == CFC_MODE_XDP)
         return sums;
-    const WsLayout w = ws_layout(n, T, mode, ct);
-    const CountArgs C = count_args(ws, w, T, g_ctr + 2ull * T.n_ctr, mode, ct);
     if (ct && T.ct_st && w.ctp_nv) {
         char *b = reinterpret_cast<char *>(ws);
         uint64_t *rec = reinterpret_cast<uint64_t *>(b + w.ctp_rec);
@@ -2157,29 +2297,44 @@ bool launch_counters(const DevTables &T, const uint32_t *meta, const uint8_t *tf
     // the histogram jobs: policy ranges of each stage, identity ranges
     std::vector<HistJob> jobs;
     uint64_t poff = 0;
-    auto add_jobs = [&](const uint32_t *keys, uint32_t nkeys, uint32_t kind,
-                        uint32_t packed) {
-        for (uint32_t lo = 0; lo < nkeys; lo += HIST_RANGE) {
-            HistJob j{keys, poff, lo, std::min(HIST_RANGE, nkeys - lo), kind, packed};
-            poff += (uint64_t)w.nblk * j.cnt;
-            jobs.push_back(j);
-        }
+    // a job over one key array: dense (a word per header) or the classify
+    // launch's compact regions, either way in w.nblk slices
+    const KeyRegions KG = key_regions(n, w.key_pb);
+    auto job = [&](const uint32_t *keys, uint32_t lo, uint32_t cnt, uint32_t kind,
+                   uint32_t packed, bool compact) {
+        HistJob j{};
+        j.keys = keys;
+        j.poff = poff;
+        j.lo = lo;
+        j.cnt = cnt;
+        j.kind = kind;
+        j.packed = packed;
+        j.compact = compact;
+        j.cap = compact ? KG.cap : 0u;
+        j.counts = compact ? keys + KG.counts() : nullptr;
+        j.n = compact ? KG.extent : n;
+        j.per_block = hist_per_block(j.n, w.nblk);
+        poff += (uint64_t)w.nblk * j.cnt;
+        jobs.push_back(j);
     };
-    add_jobs(C.ctr, T.n_ctr, 0, C.ctr_packed);
+    auto add_jobs = [&](const uint32_t *keys, uint32_t nkeys) {
+        for (uint32_t lo = 0; lo < nkeys; lo += HIST_RANGE)
+            job(keys, lo, std::min(HIST_RANGE, nkeys - lo), 0, C.ctr_packed,
+                (C.compact & KEYS_CTR) != 0);
+    };
+    add_jobs(C.ctr, T.n_ctr);
     if (mode == CFC_MODE_EGRESS)
-        add_jobs(C.ctr2, T.n_ctr, 0, C.ctr_packed);
+        add_jobs(C.ctr2, T.n_ctr);
     for (uint32_t r = 0; r < ID_RANGES; r++) {   // the identity ranges in use
         if (!((T.id_cover >> r) & 1))
             continue;
         const uint32_t lo = 2 * r * ID_RANGE;
-        HistJob j{C.id, poff, lo, std::min(2 * ID_RANGE, 2 * ID_PACK_LIMIT - lo), 1, 1};
-        poff += (uint64_t)w.nblk * j.cnt;
-        jobs.push_back(j);
+        job(C.id, lo, std::min(2 * ID_RANGE, 2 * ID_PACK_LIMIT - lo), 1, 1,
+            (C.compact & KEYS_ID) != 0);
     }
     if (jobs.empty())
         return sums;
     uint32_t *partial = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(ws) + w.partial);
-    const uint64_t per_block = hist_per_block(n, w.nblk);
     set_lds_limit((const void *)k_hist, (int)(HIST_ESC_BYTES + 4 * HIST_RANGE));
     const uint32_t id_dir = mode == CFC_MODE_EGRESS ? ID_DIR_EGRESS : ID_DIR_INGRESS;
     for (size_t a = 0; a < jobs.size(); a += HIST_JOBS_MAX) {
@@ -2191,8 +2346,8 @@ bool launch_counters(const DevTables &T, const uint32_t *meta, const uint8_t *tf
             cmax = std::max(cmax, J.j[k].cnt);
         }
         hipLaunchKernelGGL(k_hist, dim3(w.nblk, nj), dim3(BLOCK),
-                           HIST_ESC_BYTES + 4ull * cmax, s, J, meta, n, per_block, partial,
-                           g_ctr, C.g_id, id_dir);
+                           HIST_ESC_BYTES + 4ull * cmax, s, J, meta, partial, g_ctr, C.g_id,
+                           id_dir);
         hipLaunchKernelGGL(k_hist_reduce,
                            dim3((cmax + 255) / 256, nj, (w.nblk + REDUCE_ROWS - 1) / REDUCE_ROWS),
                            dim3(256), 0, s, J, partial, w.nblk, g_ctr, C.g_id, id_dir);

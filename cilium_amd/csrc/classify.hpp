@@ -129,6 +129,67 @@ constexpr uint32_t ID_PACK_LIMIT = 32768;        // identity << 1 | drop < 2^16
 constexpr uint32_t ID_RANGES = (ID_PACK_LIMIT + ID_RANGE - 1) / ID_RANGE;
 __host__ __device__ inline uint32_t id_range_of(uint32_t ident) { return ident / ID_RANGE; }
 
+// ---- compact key streams (k_classify_v4 -> k_hist)
+// Most packed key words are KEY_NONE (a header bumps an identity counter only
+// behind a policy lookup, a policy entry only on a match), so the IPv4
+// classify kernel stores the live words alone, compacted per wave, and k_hist
+// reads each run up to its count.
+//
+// A workgroup handles per_block consecutive headers (a multiple of BLOCK) and
+// its wave w the positions base + w * 64 + lane of every BLOCK-sized step:
+// exactly per_block / KEY_WAVES positions.  So (workgroup g, wave w) owns
+// region r = g * KEY_WAVES + w of `cap` words at word r * cap of the key
+// array — inside the workgroup's own [g * per_block, (g + 1) * per_block) —
+// and appends its live words there in header order.  A region can never
+// overflow, and only its wave writes it: the append cursor is a wave-uniform
+// scalar, without atomics or LDS.  The region's count goes to
+// counts()[r], a u32 array behind the regions in the same allocation; every
+// wave of every launched workgroup stores its count (zero included), so the
+// counts need no clearing.
+//
+// The words of a region at or past its count are whatever an earlier batch
+// left there: a reader masks every word by the count and never expects
+// KEY_NONE.  Position i of the flat [0, extent) space is live iff
+// i % cap < count[i / cap].
+constexpr uint32_t KEY_WAVES = BLOCK / 64;
+struct KeyRegions {
+    uint64_t extent;    // words of all regions: grid * per_block
+    uint32_t cap;       // words per region: per_block / KEY_WAVES, a multiple of 64
+    uint32_t regions;   // grid * KEY_WAVES: entries of the count array
+    __host__ __device__ uint64_t base(uint32_t r) const { return (uint64_t)r * cap; }
+    // first word of the count array, from the key array's start
+    __host__ __device__ uint64_t counts() const { return extent; }
+    // words the key array needs: regions, then counts (a multiple of 4)
+    __host__ __device__ uint64_t words() const { return extent + ((regions + 3u) & ~3u); }
+};
+// the regions of `grid` workgroups of per_block headers (a non-zero multiple
+// of BLOCK): what the kernel derives from its own launch geometry
+__host__ __device__ inline KeyRegions key_regions_grid(uint64_t grid, uint64_t per_block)
+{
+    KeyRegions g;
+    g.extent = grid * per_block;
+    g.cap = (uint32_t)(per_block / KEY_WAVES);
+    g.regions = (uint32_t)(grid * KEY_WAVES);
+    return g;
+}
+// n headers in workgroups of per_block: the launch has ceil(n / per_block)
+// workgroups, each with at least one header
+__host__ __device__ inline KeyRegions key_regions(uint64_t n, uint64_t per_block)
+{
+    return key_regions_grid((n + per_block - 1) / per_block, per_block);
+}
+// headers per workgroup of an IPv4 classify launch: nwg workgroups fill the
+// device, a contiguous slice each, rounded to whole loop iterations of `step`
+// headers (a multiple of BLOCK) and kept below 2^30 (32-bit byte offsets in
+// the kernel)
+__host__ __device__ inline uint64_t key_per_block(uint64_t n, uint64_t nwg, uint64_t step)
+{
+    uint64_t per_block = (n + nwg - 1) / nwg;
+    per_block = (per_block + step - 1) / step * step;
+    const uint64_t top = (1ull << 30) / step * step;
+    return per_block < top ? per_block : top;
+}
+
 // Per-launch pointers of the counter keys and the counter block.
 struct CountArgs {
     uint32_t *ctr;       // policy key per header (stage 1)
@@ -139,7 +200,12 @@ struct CountArgs {
     uint64_t *g_met;     // metrics block
     uint64_t *g_id;      // identity block
     uint32_t ctr_packed; // policy keys packed with len
+    // (host) KEYS_*: the key arrays k_classify_v4 wrote as compact regions
+    // (key_regions: ctr / ctr2 when packed, classify.hip CFC_KEYS_COMPACT;
+    // the IPv6 kernel's stay dense)
+    uint32_t compact;
 };
+constexpr uint32_t KEYS_CTR = 1, KEYS_ID = 2;   // CountArgs.compact: ctr / ctr2, id
 
 // Optional per-call timing (CFC_OPT_TIMING): events recorded on the launch
 // stream before the classify kernel, after it, and after the counter
@@ -150,10 +216,13 @@ struct LaunchTiming {
 };
 
 // Workspace of one launch over n headers: the key arrays of CountArgs, then
-// the histogram's partial slabs.
+// the histogram's partial slabs.  ctr, ctr2 and id hold either one word per
+// header or the compact regions and counts of an IPv4 launch on num_cus CUs
+// (key_regions), so they are sized for the larger.
 struct WsLayout {
     size_t ctr, ctr2, id, ct, ct2, partial, total;   // byte offsets / size
     uint32_t nblk;                                    // histogram slices
+    uint64_t key_pb;                                  // key_per_block of the launch
     // CT accounting by key range (launch_counters): staged records (and,
     // after the fine sort, the same space again), the coarse-sorted records,
     // per-(coarse bucket, chunk) counts and their scan, the fine-sort plan
@@ -162,9 +231,10 @@ struct WsLayout {
                                                       // coarse buckets, fine chunks
     size_t lb;   // EGRESS with a load balancer: tda, tpt, psa, pda, ppt, fl
 };
-WsLayout ws_layout(uint64_t n, const DevTables &T, int mode, bool ct);
+WsLayout ws_layout(uint64_t n, const DevTables &T, int mode, bool ct, int num_cus);
+// v4: the IPv4 kernel's launch (compact key streams)
 CountArgs count_args(uint32_t *ws, const WsLayout &w, const DevTables &T,
-                     uint64_t *g_met, int mode, bool ct);
+                     uint64_t *g_met, int mode, bool ct, bool v4);
 // LDS image of the classify kernel for these tables (must be <= 160 KiB).
 size_t classify_lds_bytes(const DevTables &T);
 
@@ -656,9 +726,10 @@ int launch_classify_v4(const DevTables &T, const cfc_hdr_v4 &in,
 // the workspace (both families): policy entries, identities, CT accounting.
 // returns true when the accounting reduce wrote T.ct_sum (the launch's
 // plain-hit summaries; tf: the batch's TCP flags, or null)
+// C, w: the classify launch's (C.compact: which key arrays hold regions)
 bool launch_counters(const DevTables &T, const uint32_t *meta, const uint8_t *tf, uint64_t n,
                      int mode, uint32_t *workspace, uint64_t *g_ctr,
-                     hipStream_t stream, bool ct);
+                     hipStream_t stream, bool ct, const CountArgs &C, const WsLayout &w);
 
 int launch_classify_v6(const DevTables &T, const cfc_hdr_v6 &in,
                        const cfc_out &out, int mode, const EgressArgs &E,

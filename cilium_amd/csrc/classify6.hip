@@ -769,8 +769,8 @@ int launch_classify_v6(const DevTables &T, const cfc_hdr_v6 &in,
     if (tm)
         (void)hipEventRecord(tm->ev[0], s);
     const bool ct = T.ct6 || out.ct;
-    const WsLayout w = ws_layout(in.n, T, mode, ct);
-    const CountArgs C = count_args(ws, w, T, g_ctr + 2ull * T.n_ctr, mode, ct);
+    const WsLayout w = ws_layout(in.n, T, mode, ct, num_cus);
+    const CountArgs C = count_args(ws, w, T, g_ctr + 2ull * T.n_ctr, mode, ct, false);
 #define CFC_LAUNCH6(M)                                                         \
     (ct ? launch_mode6<M, true>(T, in, out, E, C, grid, per_block, s, tr_id)   \
         : launch_mode6<M, false>(T, in, out, E, C, grid, per_block, s, tr_id))
@@ -784,7 +784,8 @@ int launch_classify_v6(const DevTables &T, const cfc_hdr_v6 &in,
 #undef CFC_LAUNCH6
     if (tm)
         (void)hipEventRecord(tm->ev[1], s);
-    const bool sums = launch_counters(T, in.meta, in.tcp_flags, in.n, mode, ws, g_ctr, s, ct);
+    const bool sums = launch_counters(T, in.meta, in.tcp_flags, in.n, mode, ws, g_ctr, s, ct,
+                                      C, w);
     if (E.sums)
         *E.sums = sums;
     if (tm)
