@@ -21,6 +21,8 @@ OPT_LPM4, OPT_TIMING, OPT_CT_APPLY, OPT_CT_EVICT = 1, 2, 3, 4
 OPT_LPM4_DIR_BITS = 5
 OPT_POL_PLACEMENT = 6
 POL_PLACEMENT_AUTO, POL_PLACEMENT_LINEAR, POL_PLACEMENT_DIRECT = 0, 1, 2
+OPT_PROXY_APPLY = 7
+PROXY_APPLY_COMMIT, PROXY_APPLY_DEVICE = 0, 1
 CT_APPLY_DEVICE, CT_APPLY_HOST = 0, 1
 LPM4_AUTO, LPM4_DIR24_8, LPM4_TRIE = 0, 1, 2
 
@@ -42,6 +44,7 @@ EXPORTS = (
     "cfc_proxy_apply_v4", "cfc_proxy_apply_v6", "cfc_lpm4_dir_stats",
     "cfc_pol_placement",
     "cfc_classify_from_host_v4", "cfc_classify_from_host_v6",
+    "cfc_proxy_table_stats",
 )
 # CT byte (cfc_out.ct): per stage (bits 0-3, then 4-7 for the destination's
 # ingress lookup after egress local delivery)
@@ -159,6 +162,14 @@ class ProxyStats(ctypes.Structure):
                 ("failed", ctypes.c_uint64)]
 
 
+class ProxyTableStat(ctypes.Structure):
+    """cfc_proxy_table_stat (cfc_proxy_table_stats): one family's device
+    table behind the from-host lookups"""
+    _fields_ = [("slots", ctypes.c_uint32), ("entries", ctypes.c_uint32),
+                ("patched", ctypes.c_uint64), ("rebuilt", ctypes.c_uint64),
+                ("inserted", ctypes.c_uint64), ("updated", ctypes.c_uint64)]
+
+
 class Lpm4DirStat(ctypes.Structure):
     """cfc_lpm4_dir_stat (cfc_lpm4_dir_stats): one directory width"""
     _fields_ = [("prefixes", ctypes.c_uint64), ("unresolved", ctypes.c_uint64),
@@ -239,6 +250,8 @@ def lib():
         L.cfc_classify_from_host_v6.argtypes = [vp, ctypes.POINTER(HdrV6),
                                                 ctypes.POINTER(RevproxyCols),
                                                 ctypes.POINTER(Out), vp]
+    if hasattr(L, "cfc_proxy_table_stats"):
+        L.cfc_proxy_table_stats.argtypes = [vp, i32, ctypes.POINTER(ProxyTableStat)]
     L.cfc_strerror.argtypes = [i32]
     L.cfc_strerror.restype = ctypes.c_char_p
     _lib = L

@@ -88,8 +88,21 @@ struct GLb {           // load balancing: services, reverse NAT
 struct GRp {           // the proxy maps as reverse_proxy looks them up (layout.h RevTables)
     DevBuf rp4, rp4_val, rp6, rp6_val;
     RevTables R{};
+    // keys in each table: as built, plus the device upserts' inserts
+    // (cfc_proxy_apply_* under CFC_PROXY_APPLY_DEVICE; [1]: IPv6)
     uint32_t n_rp4 = 0, n_rp6 = 0;
     uint64_t bytes = 0;
+    uint32_t slots(bool v6) const
+    {
+        return v6 ? (R.rp6 ? R.rp6_mask + 1 : 0) : (R.rp4 ? R.rp4_mask + 1 : 0);
+    }
+    uint32_t &entries(bool v6) { return v6 ? n_rp6 : n_rp4; }
+    // the upsert's view of one family's table
+    RevWriter writer(bool v6) const
+    {
+        return v6 ? RevWriter{(uint4 *)rp6.p, rp6_val.p, R.rp6_mask}
+                  : RevWriter{(uint4 *)rp4.p, rp4_val.p, R.rp4_mask};
+    }
 };
 struct GCt {           // conntrack
     CtTab<Ct4Slot> t4;   // per family (ctmirror.hpp): the table, its host mirror
@@ -301,6 +314,19 @@ struct cfc_ctx {
     hipEvent_t px_done = nullptr;
     hipStream_t px_stream = nullptr;
     bool px_pending = false;
+    // CFC_OPT_PROXY_APPLY device: cfc_proxy_apply_* upserts its records into
+    // the family's live reverse-proxy table (rpapply.hip).  The absent-key
+    // list and the two counts; the event after the last upsert (a from-host
+    // pass on another stream waits on it); per family ([1]: IPv6) what the
+    // calls did since the context opened
+    int px_apply_mode = CFC_PROXY_APPLY_COMMIT;
+    DevBuf rp_list, rp_cnt;
+    hipEvent_t rp_done = nullptr;
+    hipStream_t rp_stream = nullptr;
+    bool rp_pending = false;
+    struct {
+        uint64_t patched = 0, rebuilt = 0, inserted = 0, updated = 0;
+    } rp_stat[2];
 
     // CFC_OPT_TIMING: events of the launches since the last collect
     bool timing = false;
@@ -1276,17 +1302,21 @@ bool patch_ct(cfc_ctx *c, hipStream_t s)
 }
 
 // proxy: an explicit cfc_commit — the only commit that re-flattens the proxy
-// maps' table once an epoch exists (cfc.h "From-host batches": the reverse
-// lookups see the maps as of the last cfc_commit, and a classify's
-// auto-commit behind every cfc_proxy_apply_* would rebuild it per batch)
-int commit_locked(cfc_ctx *c, hipStream_t s, bool proxy = false)
+// maps' table because a map changed, once an epoch exists (cfc.h "From-host
+// batches": the reverse lookups see the maps as of the last cfc_commit, and a
+// classify's auto-commit behind every cfc_proxy_apply_* would rebuild it per
+// batch)
+// rebuild_proxy: re-flatten the proxy maps' table even when no proxy map
+// changed since it was built (a cfc_proxy_apply_* under CFC_PROXY_APPLY_DEVICE
+// whose records the live table cannot take in place)
+int commit_locked(cfc_ctx *c, hipStream_t s, bool proxy = false, bool rebuild_proxy = false)
 {
     reap_retired(c);
     uint64_t sig[NGROUPS];
     group_sigs(c, sig);
     if (c->epoch && !proxy)
         sig[6] = c->built_sig[6];
-    unsigned groups = 0;
+    unsigned groups = rebuild_proxy ? (unsigned)GROUP_PROXY : 0u;
     bool touched = false;
     for (int g = 0; g < NGROUPS; g++)
         if (!c->epoch || sig[g] != c->built_sig[g])
@@ -1496,6 +1526,7 @@ int cfc_open(int device, cfc_ctx **out)
         (void)hipEventCreateWithFlags(&c->last_done, hipEventDisableTiming);
         (void)hipEventCreateWithFlags(&c->nt_done, hipEventDisableTiming);
         (void)hipEventCreateWithFlags(&c->px_done, hipEventDisableTiming);
+        (void)hipEventCreateWithFlags(&c->rp_done, hipEventDisableTiming);
     }
     // the datapath owns cilium_metrics (bpf/lib/maps.h:35-41)
     auto m = std::make_unique<Map>();
@@ -1539,6 +1570,8 @@ void cfc_close(cfc_ctx *c)
         (void)hipEventDestroy(c->nt_done);
     if (c->px_done)
         (void)hipEventDestroy(c->px_done);
+    if (c->rp_done)
+        (void)hipEventDestroy(c->rp_done);
     delete c;
 }
 
@@ -1579,6 +1612,13 @@ int cfc_set_option(cfc_ctx *c, int option, int64_t value)
         if (value != 0 && value != 1)
             return -EINVAL;
         c->ct_evict = value != 0;
+        return 0;
+    case CFC_OPT_PROXY_APPLY:
+        if (value != CFC_PROXY_APPLY_COMMIT && value != CFC_PROXY_APPLY_DEVICE)
+            return -EINVAL;
+        c->px_apply_mode = (int)value;
+        // (tables built from here on leave room for the in-place inserts)
+        c->opts.rp_quarter = value == CFC_PROXY_APPLY_DEVICE;
         return 0;
     default:
         return -EINVAL;
@@ -2516,6 +2556,9 @@ int classify_from_host(cfc_ctx *c, const Hdr *in, const cfc_revproxy_cols *tr,
     if (tr->hits && table && n && hipMemsetAsync(tr->hits, 0, 8, s) != hipSuccess)
         return -EIO;
     if (table && n) {
+        // a device upsert into the table still running on another stream
+        if (c->rp_pending && c->rp_stream != s)
+            (void)hipStreamWaitEvent(s, c->rp_done, 0);
         RevArgs A{in->saddr, in->daddr, in->ports, in->meta, in->mark, tr->saddr,
                   tr->ports, tr->mark, tr->identity, (unsigned long long *)tr->hits, n};
         if ((rc = launch_revproxy(E.T, R, A, V6, c->num_cus, s)))
@@ -2711,6 +2754,17 @@ int proxy_entries(cfc_ctx *c, const Hdr *in, const cfc_out *out, int mode, uint1
     hipStream_t s = (hipStream_t)stream;
     if (apply)
         *st = cfc_proxy_stats{};
+    // CFC_PROXY_APPLY_DEVICE: the records also go into the family's live
+    // reverse-proxy table.  sig_eq: that table is up to date with the maps
+    // as they stand (no host-side change waits for a commit)
+    const bool dev = apply && c->px_apply_mode == CFC_PROXY_APPLY_DEVICE;
+    const bool v6 = family == 6;
+    bool sig_eq = false;
+    if (dev && c->epoch) {
+        uint64_t sig[NGROUPS];
+        group_sigs(c, sig);
+        sig_eq = sig[6] == c->built_sig[6];
+    }
     // the workspace is shared: order this call after the previous one
     if (c->px_pending && c->px_stream != s)
         (void)hipStreamWaitEvent(s, c->px_done, 0);
@@ -2794,11 +2848,40 @@ int proxy_entries(cfc_ctx *c, const Hdr *in, const cfc_out *out, int mode, uint1
     c->px_pending = true;
     if (!apply)
         return 0;
+    // in place when the family has a table that stays at most half full with
+    // every record a new key (an upper bound: the exact count of inserts
+    // comes back below, with the records, behind the one wait the call has)
+    // and the map has room for every record: a key it would refuse must not
+    // become visible, and the host learns of a refusal only after the upsert
+    GRp *rp = dev && c->epoch ? c->epoch->rp.get() : nullptr;
+    bool patched = false;
+    uint32_t upcnt[2] = {0, 0};   // keys inserted, keys overwritten
+    if (rp && entries && rp->slots(v6) && rp->entries(v6) + entries <= rp->slots(v6) / 2 &&
+        pm->kv.size() + entries <= pm->max_entries) {
+        if ((rc = c->rp_list.ensure(entries * 4)) || (rc = c->rp_cnt.ensure(8)))
+            return rc;
+        uint32_t *cnt2 = reinterpret_cast<uint32_t *>(c->rp_cnt.p);
+        if (hipMemsetAsync(cnt2, 0, 8, s) != hipSuccess)
+            return -EIO;
+        if ((rc = launch_rp_upsert(rp->writer(v6), v6, a.rec, (uint32_t)entries,
+                                   reinterpret_cast<uint32_t *>(c->rp_list.p), cnt2, s)))
+            return rc;
+        (void)hipEventRecord(c->rp_done, s);
+        c->rp_stream = s;
+        c->rp_pending = true;
+        note_stream(c, s);
+        if (hipMemcpyAsync(upcnt, cnt2, 8, hipMemcpyDeviceToHost, s) != hipSuccess)
+            return -EIO;
+        patched = true;
+    }
     std::vector<uint8_t> host(entries * rsz);
     if (hipMemcpyAsync(host.data(), a.rec, host.size(), hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
         return -EIO;
     c->px_pending = false;
+    c->rp_pending = false;
+    if (patched)   // (the table holds them, whatever becomes of the call)
+        rp->entries(v6) += upcnt[0];
     st->entries = entries;
     const size_t voff = family == 6 ? offsetof(cfc_proxy6_entry, value)
                                     : offsetof(cfc_proxy4_entry, value);
@@ -2815,6 +2898,24 @@ int proxy_entries(cfc_ctx *c, const Hdr *in, const cfc_out *out, int mode, uint1
         else
             st->created++;
     }
+    if (!dev || !entries)
+        return 0;
+    if (patched) {   // (the map had room for every record: none was refused)
+        c->rp_stat[v6].patched++;
+        c->rp_stat[v6].inserted += upcnt[0];
+        c->rp_stat[v6].updated += upcnt[1];
+        if (sig_eq) {   // still up to date: the next cfc_commit has nothing to rebuild
+            uint64_t sig[NGROUPS];
+            group_sigs(c, sig);
+            c->built_sig[6] = sig[6];
+        }
+        return 0;
+    }
+    // no table yet, too full, or a map that may have refused a key: the
+    // table again from the maps as they stand now
+    if ((rc = commit_locked(c, s, true, true)))
+        return rc;
+    c->rp_stat[v6].rebuilt++;
     return 0;
 }
 
@@ -2852,6 +2953,26 @@ int cfc_proxy_apply_v6(cfc_ctx *c, const cfc_hdr_v6 *in, const cfc_out *out, int
     return st ? proxy_entries(c, in, out, mode, ep_lxc, nullptr, nullptr, 0, nullptr, st,
                               stream, 6)
               : -EINVAL;
+}
+
+int cfc_proxy_table_stats(cfc_ctx *c, int family, cfc_proxy_table_stat *st)
+{
+    if (!c || !st || (family != 4 && family != 6))
+        return -EINVAL;
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    if (c->device == CFC_DEVICE_NONE)
+        return -ENODEV;
+    const bool v6 = family == 6;
+    *st = cfc_proxy_table_stat{};
+    if (c->epoch && c->epoch->rp->slots(v6)) {
+        st->slots = c->epoch->rp->slots(v6);
+        st->entries = c->epoch->rp->entries(v6);
+    }
+    st->patched = c->rp_stat[v6].patched;
+    st->rebuilt = c->rp_stat[v6].rebuilt;
+    st->inserted = c->rp_stat[v6].inserted;
+    st->updated = c->rp_stat[v6].updated;
+    return 0;
 }
 
 int cfc_counters_device(cfc_ctx *c, uint64_t **dev, uint64_t *n)

@@ -706,6 +706,15 @@ struct RevArgs {
 int launch_revproxy(const DevTables &T, const RevTables &R, const RevArgs &A, bool v6,
                     int num_cus, hipStream_t s);
 
+// The device upsert of a cfc_proxy_apply_* batch's n records (rec: the device
+// cfc_proxy4_entry / cfc_proxy6_entry array launch_proxy_write filled, distinct
+// keys) into one family's live table (rpapply.hip): keys it holds get their
+// value overwritten, the others take a free slot.  The caller keeps the table
+// at most half full with the n records in.  list: n u32 of scratch; cnt: two
+// u32, zeroed by the caller: [0] += keys inserted, [1] += keys overwritten.
+int launch_rp_upsert(const RevWriter &W, bool v6, const void *rec, uint32_t n, uint32_t *list,
+                     uint32_t *cnt, hipStream_t s);
+
 // dst[i] += src[i] for n u64 (counter import)
 int launch_add_u64(uint64_t *dst, const uint64_t *src, uint64_t n,
                    hipStream_t stream);

@@ -794,8 +794,15 @@ static void build_ct(const std::vector<const Map *> &cts, HostImage *img)
 // the reference loads the packet's first L4 word into them; the pad byte of
 // a key is not compared (the datapath's keys have it 0, and so have the
 // entries ipv{4,6}_redirect_to_host_port writes: others are left out).
-void build_revproxy(const Map *p4, const Map *p6, HostImage *img)
+void build_revproxy(const Map *p4, const Map *p6, HostImage *img, bool quarter)
 {
+    // slots for n entries of slot_bytes each: 4 n where that fits, else 2 n
+    // (0: not even that)
+    auto slots_for = [quarter](uint64_t n, uint64_t slot_bytes) -> uint64_t {
+        if (quarter && 4 * n * slot_bytes <= RP_MAX_TABLE_BYTES / 4)
+            return 4 * n;
+        return 2 * n * slot_bytes <= RP_MAX_TABLE_BYTES / 4 ? 2 * n : 0;
+    };
     img->rp4.clear();
     img->rp4_val.clear();
     img->rp6.clear();
@@ -803,8 +810,8 @@ void build_revproxy(const Map *p4, const Map *p6, HostImage *img)
     img->rp4_mask = img->rp6_mask = img->n_rp4 = img->n_rp6 = 0;
     img->rp_too_big = false;
     if (p4 && p4->ksz == 10 && p4->vsz == 16 && !p4->kv.empty()) {
-        const uint64_t ns64 = 2ull * p4->kv.size();
-        if (ns64 * 16 > RP_MAX_TABLE_BYTES / 4) {
+        const uint64_t ns64 = slots_for(p4->kv.size(), 16);
+        if (!ns64) {
             img->rp_too_big = true;
             return;
         }
@@ -837,8 +844,8 @@ void build_revproxy(const Map *p4, const Map *p6, HostImage *img)
         }
     }
     if (p6 && p6->ksz == 22 && p6->vsz == 28 && !p6->kv.empty()) {
-        const uint64_t ns64 = 2ull * p6->kv.size();
-        if (ns64 * 32 > RP_MAX_TABLE_BYTES / 4) {
+        const uint64_t ns64 = slots_for(p6->kv.size(), 32);
+        if (!ns64) {
             img->rp_too_big = true;
             return;
         }
@@ -943,7 +950,7 @@ void build_image(const std::vector<Map *> &maps, const BuildOpts &opt,
             else if (m->role == ROLE_PROXY6)
                 p6 = m;
         }
-        build_revproxy(p4, p6, img);
+        build_revproxy(p4, p6, img, opt.rp_quarter);
     }
     const Map *ipc = nullptr, *lxc = nullptr, *pf4fix = nullptr,
               *pf4dyn = nullptr, *pf6fix = nullptr, *pf6dyn = nullptr;

@@ -42,6 +42,9 @@ struct BuildOpts {
     int lpm4 = LPM4_AUTO;
     int lpm4_dir_bits = 0;   // 0 = auto, or 16..18
     int pol_placement = POL_PLACE_AUTO;
+    // the proxy maps' tables at 1/4 load instead of 1/2 where they fit
+    // (CFC_OPT_PROXY_APPLY device: room for the in-place inserts)
+    bool rp_quarter = false;
 };
 
 // IPv6 LPM (layout.h Lpm6), host side
@@ -165,8 +168,9 @@ enum : unsigned {
     GROUP_PROXY = 64,     // cilium_proxy4, cilium_proxy6 (reverse_proxy's table)
     GROUP_ALL = 127,
 };
-// the proxy maps (either may be null) into img's rp4 / rp6 tables
-void build_revproxy(const Map *p4, const Map *p6, HostImage *img);
+// the proxy maps (either may be null) into img's rp4 / rp6 tables; quarter:
+// sized for 1/4 load where RP_MAX_TABLE_BYTES allows, else for 1/2
+void build_revproxy(const Map *p4, const Map *p6, HostImage *img, bool quarter = false);
 // host reference of the device lookup (unit tests): the slot of the key
 // {saddr, ports (dport | sport << 16), nexthdr} in a built table, or -1
 int64_t rp4_find_slot(const HostImage &img, uint32_t saddr, uint32_t ports, uint32_t nexthdr);

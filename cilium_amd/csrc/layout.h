@@ -458,8 +458,11 @@ __host__ __device__ inline uint32_t lb6_hash(uint32_t a0, uint32_t a1, uint32_t 
 //                   orig_daddr}; rp4_val[slot] = orig_dport (be16 raw)
 //   v6 slot (32 B): {saddr words raw}, {dport | sport << 16, nexthdr |
 //                   RP_USED, orig_dport, 0}; rp6_val[slot] = orig_daddr (raw)
-// The value arrays are read on a hit only.  The tables are static per epoch
+// The value arrays are read on a hit only.  The tables are built per epoch
 // (flatten.cpp build_revproxy); a family without entries has none (null).
+// Between rebuilds the device upsert of cfc_proxy_apply_* (rpapply.hip,
+// through RevWriter) overwrites values and fills free slots in place; there
+// are no tombstones, a delete reaches the table through a rebuild.
 // Not part of DevTables: only the reverse-proxy pass (revproxy.hip) reads it.
 constexpr uint32_t RP_USED = 1u << 8;
 __host__ __device__ inline uint32_t rp4_hash(uint32_t saddr, uint32_t ports, uint32_t nexthdr)
@@ -477,6 +480,13 @@ struct RevTables {
     const uint4 *rp6;              // 2 uint4 per slot; null: cilium_proxy6 empty
     const uint4 *rp6_val;
     uint32_t rp4_mask, rp6_mask;   // slots - 1
+};
+// one family's table as the device upsert writes it (rpapply.hip); val: u32
+// per slot (IPv4), uint4 per slot (IPv6)
+struct RevWriter {
+    uint4 *tab;
+    void *val;
+    uint32_t mask;
 };
 // bytes a raw 16-byte table load may address (kern_common.hpp ldt16)
 constexpr uint64_t RP_MAX_TABLE_BYTES = 1ull << 31;

@@ -304,7 +304,9 @@ class Datapath:
     def set_option(self, option, value):
         """cfc_set_option: L.OPT_LPM4 (ipcache layout, next commit),
         L.OPT_LPM4_DIR_BITS (its directory width, next commit),
-        L.OPT_POL_PLACEMENT (policy key placement, next commit) or
+        L.OPT_POL_PLACEMENT (policy key placement, next commit),
+        L.OPT_PROXY_APPLY (L.PROXY_APPLY_DEVICE: proxy_apply's entries translate
+        in the next classify_from_host without a commit) or
         L.OPT_TIMING (per-call kernel events)."""
         L.check(self.L.cfc_set_option(self.h, option, value), "set option")
 
@@ -413,7 +415,8 @@ class Datapath:
         """cfc_classify_from_host_v4/v6: reverse_proxy over a from-host batch
         (the L7 proxy's packets towards an endpoint get the source of the
         connection the proxy stands in for, from cilium_proxy4/6 as of the
-        last commit()), then INGRESS classification of the translated batch
+        last commit() — under L.PROXY_APPLY_DEVICE also every proxy_apply
+        since), then INGRESS classification of the translated batch
         -> (Verdicts, Translated).  Translated.batch is the header batch to
         hand to ct_apply, monitor_events, drop_notify and proxy_entries (mode
         INGRESS).  alias=True translates in place: saddr, ports and mark are
@@ -550,6 +553,16 @@ class Datapath:
         L.check(fn(self.h, ctypes.byref(hdr_struct(batch)), ctypes.byref(out_struct(out)),
                    mode, ep_lxc, ctypes.byref(st), self._stream(stream)), "proxy apply")
         return {k: getattr(st, k) for k, _ in L.ProxyStats._fields_}
+
+    def proxy_table_stats(self, v6=False):
+        """cfc_proxy_table_stats: the family's device table behind the
+        from-host lookups and what proxy_apply did to it under
+        L.PROXY_APPLY_DEVICE -> {slots, entries, patched, rebuilt, inserted,
+        updated}"""
+        st = L.ProxyTableStat()
+        L.check(self.L.cfc_proxy_table_stats(self.h, 6 if v6 else 4, ctypes.byref(st)),
+                "proxy table stats")
+        return {k: getattr(st, k) for k, _ in L.ProxyTableStat._fields_}
 
     def set_clock(self, now):
         """cfc_set_clock: bpf_ktime_get_sec() for the next calls."""

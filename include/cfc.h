@@ -206,7 +206,14 @@ int cfc_commit(cfc_ctx *ctx, void *stream);
  * displacement exists for every key and the displacement bytes fit the
  * classify kernels' on-chip image, else LINEAR; forced DIRECT fails the
  * commit with -ENOSPC instead.  cfc_pol_placement reports what the epoch
- * took.  Lookups give the same result under both. */
+ * took.  Lookups give the same result under both.
+ * CFC_OPT_PROXY_APPLY: how the entries cfc_proxy_apply_* writes reach the
+ * device table the from-host lookups read ("From-host batches" below), from
+ * the next cfc_proxy_apply_* call on.  COMMIT (default): with the next
+ * cfc_commit.  DEVICE: the call itself folds its records into the family's
+ * live table in place (or rebuilds the table from the map when it has none,
+ * would pass half load, or the map refused a key), so they translate in
+ * every cfc_classify_from_host_* queued after it returns. */
 #define CFC_OPT_LPM4 1
 #define CFC_LPM4_AUTO 0
 #define CFC_LPM4_DIR24_8 1
@@ -221,6 +228,9 @@ int cfc_commit(cfc_ctx *ctx, void *stream);
 #define CFC_POL_PLACEMENT_AUTO 0
 #define CFC_POL_PLACEMENT_LINEAR 1
 #define CFC_POL_PLACEMENT_DIRECT 2
+#define CFC_OPT_PROXY_APPLY 7
+#define CFC_PROXY_APPLY_COMMIT 0
+#define CFC_PROXY_APPLY_DEVICE 1
 int cfc_set_option(cfc_ctx *ctx, int option, int64_t value);
 
 /* ---------------------------------------------------------------- datapath */
@@ -718,6 +728,23 @@ int cfc_proxy_apply_v6(cfc_ctx *ctx, const cfc_hdr_v6 *in, const cfc_out *out,
  * auto-commit leaves it alone once the context has tables): an entry written by cfc_proxy_apply_* or
  * through the map API translates after the next cfc_commit(), a deleted one
  * until then.  The table is rebuilt only when a proxy map changed.
+ * Under CFC_OPT_PROXY_APPLY = CFC_PROXY_APPLY_DEVICE the records of a
+ * cfc_proxy_apply_* call do not wait for that commit: after the call returns,
+ * every record the map accepted translates in any cfc_classify_from_host_*
+ * queued afterwards, on any stream (a key the map refused, st->failed, never
+ * does).  The call upserts its records into the family's live table on the
+ * device, on its `stream` — a key the table holds gets its value overwritten
+ * in its slot, a new key takes the first free slot of its probe walk — and
+ * rebuilds the table from the maps instead, as cfc_commit does (and with its
+ * return value when a table would be too large), when the family has no
+ * table yet, when the table's entries plus the batch's records would pass
+ * half of its slots, or when the map refused a key (or, being that close to
+ * max_entries, might have).  Tables built while the
+ * option is on are sized for at most 1/4 load, so growth is amortised.
+ * Other host-side changes to the proxy maps (the map API's updates and
+ * deletes, the GC) become visible at the next explicit cfc_commit() at the
+ * latest; a rebuild may show them earlier.  cfc_proxy_table_stats reports
+ * the table and what the calls did.
  *
  * CFC_MARK_TRANSLATED: bit 12 of the mark column, outside
  * MARK_MAGIC_HOST_MASK (0xF00) and outside the identity bits of a proxy mark
@@ -768,6 +795,20 @@ int cfc_classify_from_host_v4(cfc_ctx *ctx, const cfc_hdr_v4 *in,
 int cfc_classify_from_host_v6(cfc_ctx *ctx, const cfc_hdr_v6 *in,
                               const cfc_revproxy_cols *tr, const cfc_out *out,
                               void *stream);
+
+/* The family's device table behind the from-host lookups, and what the
+ * cfc_proxy_apply_* calls under CFC_PROXY_APPLY_DEVICE did to it since the
+ * context opened.  family: 4 or 6 (else, or with a NULL st, -EINVAL);
+ * -ENODEV on a host-only context.  All zeros before a table exists. */
+typedef struct {
+    uint32_t slots;      /* of the family's device table, 0 = none */
+    uint32_t entries;    /* keys in it */
+    uint64_t patched;    /* cfc_proxy_apply_* calls folded in place */
+    uint64_t rebuilt;    /* ... that rebuilt the table instead */
+    uint64_t inserted;   /* keys the in-place passes added */
+    uint64_t updated;    /* keys they overwrote */
+} cfc_proxy_table_stat;
+int cfc_proxy_table_stats(cfc_ctx *ctx, int family, cfc_proxy_table_stat *st);
 
 /* ---------------------------------------------------------------- counters */
 /* The device counter block is a flat u64 array:
