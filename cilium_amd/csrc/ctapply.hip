@@ -384,6 +384,17 @@ __global__ __launch_bounds__(256) void k_cta_scan_w(CtaArgs A)
                 if constexpr (!V6)
                     if (A.rk4)
                         A.rk4[TWO ? 2 * i + st : i] = make_uint4(o.sa, o.da, o.z2, o.w2);
+                if ((st ? r.k2 : r.k1) == NONE) {
+                    // a create the ordering pass made of a hit (no miss tag):
+                    // its key had a slot when the batch started, deleted
+                    // before this stage — a slot with hits and deletes of the
+                    // launch, which route lists before the inserts here: marked
+                    // now, so that every op on it goes to the fold in order (a
+                    // slot marked deleted only is folded from its first delete)
+                    const uint32_t ks = find(A, o.sa, o.da, o.z2, o.w2);
+                    if (ks != NONE)
+                        order_mark(A, ks, MARK_ORDERED | MARK_PUTC);
+                }
                 if (!o.is_tcp && !o.ki_form) {
                     // its related entry (ct_create4/6's second write) may
                     // overwrite a live one: route runs before the inserts
@@ -808,11 +819,13 @@ __device__ __forceinline__ ReqKey<V6> req_key_of(const CtaArgs &A, uint32_t ord)
 }
 
 // ---- insert: one thread per home slot; keys deduped in registers (a fifth
-// distinct key of one home slot is found by rescanning the run).  A key's
-// first create also writes its related ICMP entry and, with a load
-// balancer's ct_state, its reverse-NAT entry (round 1): the request is
-// marked (bit 0 of its word) and k_cta_related makes those requests — no
-// per-request atomic on a shared counter here.
+// distinct key of one home slot is found by rescanning the run).  A create
+// also writes its related ICMP entry (every create the ordering pass left:
+// a key deleted and created again writes it again; behind a service step a
+// key's first create) and, with a load balancer's ct_state, its reverse-NAT
+// entry (round 1): the request is marked (bit 0 of its word) and
+// k_cta_related makes those requests — no per-request atomic on a shared
+// counter here.
 // (1024-thread blocks for the per-request passes: one counter atomic per
 // 1024 requests)
 constexpr int RQ_B = 1024;
@@ -864,7 +877,11 @@ __global__ __launch_bounds__(RQ_B) void k_cta_insert(CtaArgs A, uint64_t *req, u
             const uint32_t c = cx_off + r;
             if (c < A.cx_cap)
                 A.cx[c] = pack(A, slot, ord);
-            if (round == 0 && first && ord_sec(ord) == SEC_OP)
+            // (the ordering pass left a create only where the reference
+            // creates: each writes its related entry again, a re-create of a
+            // key the batch deleted included, and the last one in packet order
+            // stands.  A service step's creates may repeat a key: its first)
+            if (round == 0 && (first || !A.lbr) && ord_sec(ord) == SEC_OP)
                 req[r] |= 1ull;
         }
     }
@@ -921,9 +938,14 @@ __global__ __launch_bounds__(256) void k_cta_newkeys(CtaArgs A, const uint64_t *
                 continue;
             if (nk < 4)
                 kk[nk++] = k;
-            if (find(A, k.d, k.s, k.z, k.w) != NONE)
+            // (a create of a key the table holds: the batch deleted it first,
+            // the ordering pass left the create — no new key of its own, but
+            // it writes its related entry again, which the table may lack;
+            // behind a service step it is a counted hit and writes nothing)
+            const bool have = find(A, k.d, k.s, k.z, k.w) != NONE;
+            if (have && (A.lbr || ord_sec(ord) != SEC_OP))
                 continue;
-            uint32_t nk = 1u + (ord_sec(ord) == SEC_OP && o.kx ? 1u : 0u);
+            uint32_t nk = have ? 0u : 1u + (ord_sec(ord) == SEC_OP && o.kx ? 1u : 0u);
             if (ord_sec(ord) == SEC_OP && !o.ki_form) {
                 // its related ICMP entry: one per address pair and map, which
                 // many creates share — counted once per batch (a set of the
@@ -950,7 +972,7 @@ __global__ __launch_bounds__(256) void k_cta_newkeys(CtaArgs A, const uint64_t *
             }
             nk_new += nk;
             nk_tcp += o.is_tcp ? nk : 0u;
-            if (A.emcnt) {   // the map its keys go to: its owner's, by kind
+            if (A.emcnt && nk) {   // the map its keys go to: its owner's, by kind
                 const uint32_t sel = o.owner | (o.is_tcp ? 0u : 2u);
                 for (uint32_t j = 0; j < A.n_emaps; j++)
                     if (A.emaps[j] == sel) {
@@ -965,7 +987,7 @@ __global__ __launch_bounds__(256) void k_cta_newkeys(CtaArgs A, const uint64_t *
 }
 
 // ---- related: one thread per (sorted) round-0 request; a marked one is a
-// key's first create, whose related ICMP entry goes into the device table
+// create (k_cta_insert), whose related ICMP entry goes into the device table
 // for an ANY map (UDP, ICMP echo: a round-1 request) or into the host log
 // for a TCP map (no lookup reaches it there), and whose reverse-NAT entry
 // (ct_create4 with ct_state->addr) is a round-1 request
