@@ -1246,34 +1246,121 @@ __global__ __launch_bounds__(BLOCK) void k_hist(HistJobs J, const uint32_t *meta
     }
 }
 
-// blockIdx.y: job, blockIdx.x: 256 keys of it
-// blockIdx.z: a group of REDUCE_ROWS slices
-constexpr uint32_t REDUCE_ROWS = 32;
-__global__ __launch_bounds__(256) void k_hist_reduce(HistJobs J, const uint32_t *partial,
-                                                     uint32_t nblk, uint64_t *g_ctr,
-                                                     uint64_t *g_id, uint32_t id_dir)
+// k_hist_reduce: the slabs' fields summed per key and added to the counters.
+//   blockIdx.y  the job
+//   blockIdx.z  a group of REDUCE_ROWS slices (slab rows)
+//   blockIdx.x  64 * K adjacent keys of the job
+// A workgroup's REDUCE_WAVES waves take every REDUCE_WAVES-th row of the
+// group; a lane sums K adjacent keys, REDUCE_UNROLL rows' loads in flight
+// before the first add.  The waves' sums meet in LDS, and thread t adds key
+// t's pair: one atomic pair per key and workgroup, adjacent lanes on adjacent
+// counters.  The kernel's time follows the number of those atomics and the
+// lines one atomic instruction touches, not the bytes it reads (DESIGN.md §4
+// "The counter reduce"), hence the large group.
+//   K = 4  16-byte loads.  Needs the job's slab rows 16-byte aligned: poff
+//          and cnt both multiples of 4 (the slabs start 256-byte aligned).
+//   K = 1  4-byte loads: any other job.
+// hist_reduce_vec is that rule, for the kernel and for the launch's grid.
+#ifndef CFC_REDUCE_ROWS
+#define CFC_REDUCE_ROWS 256   // (A/B builds)
+#endif
+constexpr uint32_t REDUCE_ROWS = CFC_REDUCE_ROWS;
+constexpr uint32_t REDUCE_UNROLL = 8;
+constexpr uint32_t REDUCE_WAVES = 4;
+// (a group's sums fit u32: a slot's fields are below 2^11 and 2^21)
+static_assert(REDUCE_ROWS <= 2048, "k_hist_reduce sums a group's fields in u32");
+__host__ __device__ inline bool hist_reduce_vec(uint64_t poff, uint32_t cnt)
+{
+    return ((poff | cnt) & 3) == 0;
+}
+// keys a workgroup of k_hist_reduce takes: 64 lanes of K keys
+__host__ __device__ inline uint32_t hist_reduce_keys(uint64_t poff, uint32_t cnt)
+{
+    return 64u * (hist_reduce_vec(poff, cnt) ? 4u : 1u);
+}
+
+template <uint32_t K>
+__device__ __forceinline__ void hist_reduce_job(const HistJob &jb, const uint32_t *partial,
+                                                uint32_t nblk, uint64_t *g_ctr, uint64_t *g_id,
+                                                uint32_t id_dir)
+{
+    __shared__ uint32_t s_pk[REDUCE_WAVES][64 * K], s_by[REDUCE_WAVES][64 * K];
+    const uint32_t k0 = blockIdx.x * 64 * K;
+    if (k0 >= jb.cnt)   // (uniform)
+        return;
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t j = k0 + K * lane;   // (K = 4: cnt a multiple of 4, so j + 3 < cnt behind j < cnt)
+    const uint32_t b0 = blockIdx.z * REDUCE_ROWS, b1 = min(nblk, b0 + REDUCE_ROWS);
+    uint32_t pk[K], by[K];
+#pragma unroll
+    for (uint32_t k = 0; k < K; k++)
+        pk[k] = by[k] = 0;
+    if (j < jb.cnt) {
+        const uint32_t *p = partial + jb.poff + j;
+        for (uint32_t b = b0 + wave; b < b1; b += REDUCE_WAVES * REDUCE_UNROLL) {
+            uint32_t v[REDUCE_UNROLL][K];
+#pragma unroll
+            for (uint32_t u = 0; u < REDUCE_UNROLL; u++) {   // (a row past the group: none)
+                const uint32_t row = b + REDUCE_WAVES * u;
+#pragma unroll
+                for (uint32_t k = 0; k < K; k++)
+                    v[u][k] = 0;
+                if (row < b1) {
+                    if constexpr (K == 4) {
+                        const uint4 q = ld_nt4(p + (uint64_t)row * jb.cnt);
+                        v[u][0] = q.x; v[u][1] = q.y; v[u][2] = q.z; v[u][3] = q.w;
+                    } else {
+                        v[u][0] = ld_nt(p + (uint64_t)row * jb.cnt);
+                    }
+                }
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < REDUCE_UNROLL; u++)
+#pragma unroll
+                for (uint32_t k = 0; k < K; k++) {
+                    pk[k] += (uint32_t)HistSlot::packets(v[u][k]);
+                    by[k] += (uint32_t)HistSlot::bytes(v[u][k]);
+                }
+        }
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < K; k++) {
+        s_pk[wave][K * lane + k] = pk[k];
+        s_by[wave][K * lane + k] = by[k];
+    }
+    __syncthreads();
+    // (K = 4: one iteration per thread; K = 1: the first wave alone)
+    for (uint32_t t = threadIdx.x; t < 64 * K; t += 64 * REDUCE_WAVES) {
+        if (k0 + t >= jb.cnt)
+            break;
+        uint64_t spk = 0, sby = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < REDUCE_WAVES; w++) {
+            spk += s_pk[w][t];
+            sby += s_by[w][t];
+        }
+        // (a key whose packet fields are zero may still hold bytes: the
+        // fields are what the escapes left, not the counts)
+        if (!(spk | sby))
+            continue;
+        unsigned long long *dst = hist_dst(jb, jb.lo + k0 + t, g_ctr, g_id, id_dir);
+        if (spk)
+            atomicAdd(dst, (unsigned long long)spk);
+        if (sby)
+            atomicAdd(dst + 1, (unsigned long long)sby);
+    }
+}
+
+__global__ __launch_bounds__(64 * REDUCE_WAVES) void k_hist_reduce(HistJobs J,
+                                                                   const uint32_t *partial,
+                                                                   uint32_t nblk, uint64_t *g_ctr,
+                                                                   uint64_t *g_id, uint32_t id_dir)
 {
     const HistJob jb = J.j[blockIdx.y];
-    const uint32_t j = blockIdx.x * 256 + threadIdx.x;
-    if (j >= jb.cnt)
-        return;
-    uint64_t pk = 0, by = 0;
-    const uint32_t *p = partial + jb.poff + j;
-    const uint32_t b0 = blockIdx.z * REDUCE_ROWS, b1 = min(nblk, b0 + REDUCE_ROWS);
-    for (uint32_t b = b0; b < b1; b++) {
-        const uint32_t v = ld_nt(p + (uint64_t)b * jb.cnt);
-        pk += HistSlot::packets(v);
-        by += HistSlot::bytes(v);
-    }
-    // (a key whose packet fields are zero may still hold bytes: the fields
-    // are what the escapes left, not the counts)
-    if (!(pk | by))
-        return;
-    unsigned long long *dst = hist_dst(jb, jb.lo + j, g_ctr, g_id, id_dir);
-    if (pk)
-        atomicAdd(dst, (unsigned long long)pk);
-    if (by)
-        atomicAdd(dst + 1, (unsigned long long)by);
+    if (hist_reduce_vec(jb.poff, jb.cnt))   // (uniform)
+        hist_reduce_job<4>(jb, partial, nblk, g_ctr, g_id, id_dir);
+    else
+        hist_reduce_job<1>(jb, partial, nblk, g_ctr, g_id, id_dir);
 }
 
 // CONNTRACK_ACCOUNTING: the per-header keys (slot * 2 + dir) of a
@@ -2340,17 +2427,19 @@ bool launch_counters(const DevTables &T, const uint32_t *meta, const uint8_t *tf
     for (size_t a = 0; a < jobs.size(); a += HIST_JOBS_MAX) {
         HistJobs J{};
         const uint32_t nj = (uint32_t)std::min<size_t>(HIST_JOBS_MAX, jobs.size() - a);
-        uint32_t cmax = 0;
+        uint32_t cmax = 0, rgrid = 0;   // most slots; most workgroups of a job's reduce
         for (uint32_t k = 0; k < nj; k++) {
             J.j[k] = jobs[a + k];
             cmax = std::max(cmax, J.j[k].cnt);
+            const uint32_t per = hist_reduce_keys(J.j[k].poff, J.j[k].cnt);
+            rgrid = std::max(rgrid, (J.j[k].cnt + per - 1) / per);
         }
         hipLaunchKernelGGL(k_hist, dim3(w.nblk, nj), dim3(BLOCK),
                            HIST_ESC_BYTES + 4ull * cmax, s, J, meta, partial, g_ctr, C.g_id,
                            id_dir);
         hipLaunchKernelGGL(k_hist_reduce,
-                           dim3((cmax + 255) / 256, nj, (w.nblk + REDUCE_ROWS - 1) / REDUCE_ROWS),
-                           dim3(256), 0, s, J, partial, w.nblk, g_ctr, C.g_id, id_dir);
+                           dim3(rgrid, nj, (w.nblk + REDUCE_ROWS - 1) / REDUCE_ROWS),
+                           dim3(64 * REDUCE_WAVES), 0, s, J, partial, w.nblk, g_ctr, C.g_id, id_dir);
     }
     return sums;
 }
